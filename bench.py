@@ -18,8 +18,16 @@ Strong scaling: the dataset is always 1B x 256 whatever N is.  1B x 256 bf16 = 5
 at N >= 2 every row is resident in HBM; at N = 1 the rows that do not fit in one GPU's
 HBM budget are recomputed in-kernel from their generating lineage on every pass (Spark
 MEMORY_ONLY semantics; see synthetic.py) -- every sample is still processed every
-iteration.  ``hbm_only_rows_per_s`` reports the rate over HBM-resident rows alone (what a
-real, fully resident table gets), measured by separate passes after the timed region.
+iteration.
+
+A plain run does only what the headline needs: set-up, warm-up, the timed fit, the JSON
+line.  ``--full`` adds the figures that take runs of their own after the timed region:
+``hbm_only_rows_per_s``, the rate over HBM-resident rows alone (what a real, fully
+resident table gets), and at N > 1 ``allreduce_us_per_call``; without it both are null.
+``--dump-outputs DIR`` writes what the timed fit returned (``coefficients.npy``,
+``intercept.npy``, ``objective_history.npy``, float64) so that two builds can be compared
+output for output: the data is generated from a fixed seed, so the inputs are the same
+on every run with the same arguments.
 
 Launch: ``python bench.py --gpus N`` starts N ranks itself (a child
 ``torch.distributed.run --nproc-per-node N`` process, before anything touches the GPU);
@@ -110,6 +118,15 @@ def _rccl_version():
         return None
 
 
+def _dump_outputs(path, model, hist):
+    """What a caller of the timed fit receives, one float64 array per file."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "coefficients.npy"), np.asarray(model.coefficients.toArray(), dtype=np.float64))
+    np.save(os.path.join(path, "intercept.npy"), np.asarray([model.intercept], dtype=np.float64))
+    np.save(os.path.join(path, "objective_history.npy"), np.asarray(hist, dtype=np.float64))
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("--gpus", type=int, default=1)
@@ -119,7 +136,12 @@ def main(argv=None):
     ap.add_argument("--features", type=int, default=256)
     ap.add_argument("--resident-fraction", type=float, default=None,
                     help="share of free HBM the feature cache may use (default: session conf, 0.85)")
-    ap.add_argument("--no-hbm-only", action="store_true", help="skip the resident-rows-only rate")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure, after the timed region, the resident-rows-only rate and (N > 1) the "
+                         "latency of one gradient all-reduce")
+    ap.add_argument("--no-hbm-only", action="store_true", help="with --full: skip the resident-rows-only rate")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed fit's coefficients, intercept and objective history to DIR/<name>.npy")
     ap.add_argument("--rehearsal", action="store_true",
                     help="allow N > 1 GPU ranks on a non-RCCL backend (O3S_DIST_BACKEND=gloo, ranks sharing a GPU); "
                          "the JSON is then marked rehearsal and is not a headline")
@@ -172,12 +194,14 @@ def main(argv=None):
     comm.barrier()
     elapsed = comm.max_scalar(time.perf_counter() - t)
     ar1 = tuple(COMM_STATS.get("all_reduce", (0, 0)))
-    ar_us = _allreduce_us(comm, a.features + 3, on_gpu) if comm.world_size > 1 else None
 
     hist = model.summary.objectiveHistory
+    if a.dump_outputs and comm.rank == 0:
+        _dump_outputs(a.dump_outputs, model, hist)
     setup = comm.max_scalar(float(getattr(model, "_fit_setup_seconds", 0.0)))
+    ar_us = _allreduce_us(comm, a.features + 3, on_gpu) if a.full and comm.world_size > 1 else None
     hbm_rate = None
-    if not a.no_hbm_only and resident > 0:
+    if a.full and not a.no_hbm_only and resident > 0:
         hbm_rate = _hbm_only_rate(df, comm, on_gpu)
     tot_resident = comm.sum_scalar(int(resident))
     tot_lineage = comm.sum_scalar(int(lineage))
@@ -223,7 +247,7 @@ def main(argv=None):
         "rccl_version": _rccl_version() if comm.backend == "nccl" else None,
         "rehearsal": rehearsal,
         # all-reduces issued inside the timed fit (this rank) and their payload, plus the
-        # latency of one gradient-sized all-reduce measured after the timed region
+        # latency of one gradient-sized all-reduce measured after the timed region (--full)
         "allreduce_calls_timed": ar1[0] - ar0[0],
         "allreduce_bytes_timed": ar1[1] - ar0[1],
         "allreduce_us_per_call": ar_us,

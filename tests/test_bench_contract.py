@@ -36,7 +36,8 @@ def _env():
 
 @pytest.mark.timeout(300)
 def test_bench_single_and_four_ranks_agree():
-    args = ["--steps", "3", "--warmup", "1", "--rows", "24000", "--features", "32"]
+    # --full: the resident-rows-only rate and the all-reduce latency are measured after the timed fit
+    args = ["--steps", "3", "--warmup", "1", "--rows", "24000", "--features", "32", "--full"]
     one = subprocess.run([sys.executable, "bench.py", *args], cwd=ROOT, env=_env(), capture_output=True, text=True,
                          timeout=240)
     assert one.returncode == 0, one.stderr[-2000:]
@@ -57,6 +58,35 @@ def test_bench_single_and_four_ranks_agree():
     assert abs(r4["first_loss"] - r1["first_loss"]) < 1e-9
     assert abs(r4["final_loss"] - r1["final_loss"]) < 1e-7 * abs(r1["final_loss"])
     assert r1["hbm_only_rows_per_s"] > 0 and 0 <= r1["fit_setup_share"] <= 1
+
+
+@pytest.mark.timeout(300)
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """Without --full nothing is measured after the timed fit (those figures are null), --steps
+    sets the number of timed iterations, and --dump-outputs writes what that fit returned:
+    float64 arrays that a second run with the same arguments reproduces (same seeded inputs)."""
+    import numpy as np
+    args = ["--gpus", "1", "--steps", "4", "--warmup", "1", "--rows", "12000", "--features", "16"]
+    runs = []
+    for name in ("a", "b"):
+        out = tmp_path / name
+        p = subprocess.run([sys.executable, "bench.py", *args, "--dump-outputs", str(out)], cwd=ROOT, env=_env(),
+                           capture_output=True, text=True, timeout=240)
+        assert p.returncode == 0, p.stderr[-2000:]
+        r = _json_line(p.stdout)
+        assert KEYS <= set(r) and r["steps"] == 4 and r["ms_per_step"] > 0 and r["value"] > 0
+        assert abs(r["value"] * r["ms_per_step"] * 1e-3 - 12000) < 1e-6 * 12000      # one step = one pass over the rows
+        assert r["hbm_only_rows_per_s"] is None and r["allreduce_us_per_call"] is None
+        assert sorted(f.name for f in out.iterdir()) == ["coefficients.npy", "intercept.npy", "objective_history.npy"]
+        arrs = {f.stem: np.load(f) for f in out.iterdir()}
+        assert all(v.dtype == np.float64 and np.isfinite(v).all() for v in arrs.values())
+        assert arrs["coefficients"].shape == (16,) and arrs["intercept"].shape == (1,)
+        assert arrs["objective_history"].shape == (4,)                 # one loss per timed step
+        assert arrs["objective_history"][0] == r["first_loss"] and arrs["objective_history"][-1] == r["final_loss"]
+        assert np.abs(arrs["coefficients"]).max() > 0
+        runs.append(arrs)
+    for k in runs[0]:
+        np.testing.assert_array_equal(runs[0][k], runs[1][k])
 
 
 @pytest.mark.gpu

@@ -111,6 +111,33 @@ def test_reference_tutorial_graph_maps_to_our_widgets(warehouse):
     assert len(wf.links) == 6
 
 
+def test_pickle_format_properties_are_skipped_with_a_warning(warehouse, tmp_path, caplog):
+    # this add-on's tutorial with every node renamed through the inverse of REFERENCE_WIDGETS
+    # (so the names are the table's own, not an independent check of it) and the properties of
+    # three nodes stored as an opaque pickle-format blob: each must be skipped, never loaded
+    import base64
+    import xml.etree.ElementTree as ET
+    from orangecontrib.spark_amd.workflow import REFERENCE_WIDGETS
+    upstream = {ours: theirs for theirs, ours in REFERENCE_WIDGETS.items()}
+    root = ET.parse(TUTORIAL).getroot()
+    for n in root.iter("node"):
+        qn = n.get("qualified_name")
+        n.set("qualified_name", upstream[qn[:-4] if qn.endswith("View") else qn])
+        n.set("project_name", "Orange3-spark")
+    for p in root.iter("properties"):
+        if p.get("node_id") in ("0", "3", "7"):
+            p.set("format", "pickle")
+            p.text = base64.encodebytes(b"\x80\x03not a pickle anyone may load\x00.").decode()
+    ref = str(tmp_path / "upstream_spark_ml.ows")
+    ET.ElementTree(root).write(ref, encoding="utf-8", xml_declaration=True)
+    assert all(n.get("qualified_name").startswith("orangecontrib.spark.widgets.") for n in root.iter("node"))
+    with caplog.at_level("WARNING", logger="orangecontrib.spark_amd.workflow"):
+        wf = Workflow.load(ref).instantiate()      # pickle properties are skipped, never unpickled
+    assert sum("never unpickled" in r.getMessage() for r in caplog.records) == 3
+    assert type(wf.widget("Evaluation")).__name__ == "OWEvaluation"
+    assert len(wf.links) == 6
+
+
 def test_data_widgets(warehouse):
     from orangecontrib.spark_amd.widgets.data import (owcache, owcontext, owdatabase, owfillna, owfromorange,
                                                       owfrompandas, owpandastoorange, owsample, owscript, owsql,

@@ -2,6 +2,7 @@
 # Rehearse the N = 2 shape of the scaling run on ONE GPU: 2 ranks over gloo, each holding
 # HBM-resident rows AND rows regenerated in-kernel from lineage (small resident fraction),
 # against one rank on the same 200M x 256 table -- the loss curves must agree.
+# (--no-hbm-only only matters together with --full; a plain run never measures that rate.)
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 mkdir -p gpurun_out
