@@ -78,13 +78,6 @@ def _thresholds(splits: list, F: int, device):
     return torch.from_numpy(th).to(device), Tp
 
 
-def _bin_block_kernel(X: torch.Tensor, tht, Tp, out: torch.Tensor, out_t: torch.Tensor | None, ldt: int) -> None:
-    n, F = X.shape
-    N.check(N.kernels().o3s_bin_features2(X.data_ptr(), int(X.dtype == torch.bfloat16), n, X.stride(0), F,
-                                          tht.data_ptr(), Tp, out.data_ptr(), N.ptr(out_t), ldt, N.stream_of(X)),
-            "bin_features")
-
-
 def _bin_block_torch(X: torch.Tensor, splits: list, out: torch.Tensor) -> None:
     if X.dtype == torch.bfloat16:
         X = X.float()
@@ -118,7 +111,7 @@ def bin_features(X, splits: list) -> torch.Tensor:
         if m == 0:
             return
         if tht is not None and Xb.dtype in (torch.float32, torch.bfloat16) and Xb.stride(1) == 1:
-            _bin_block_kernel(Xb, tht, Tp, out[a:a + m], out_t[:, a:] if out_t is not None else None, n)
+            T.bin_block(Xb, tht, Tp, out[a:a + m], out_t[:, a:] if out_t is not None else None, n)
         else:
             _bin_block_torch(Xb, splits, out[a:a + m])
             if out_t is not None:
@@ -132,83 +125,7 @@ def bin_features(X, splits: list) -> torch.Tensor:
     return out
 
 
-# ----------------------------------------------------------------------------- impurity
-def _sibling(parent: torch.Tensor, child: torch.Tensor, cls: bool) -> torch.Tensor:
-    """Histogram of the scanned child's sibling, parent - child ([P, F, B, S] fp64).
-
-    Both operands are exact ordered fp64 sums, but with fractional weights the
-    difference can still leave rounding residue in bins the sibling does not populate;
-    it is cleaned so such a bin reads as empty: weights / class counts are clamped at 0
-    and REG bins whose weight is not positive get zero w*y.  The REG node total of w*y^2
-    (feature 0, bin 0, stat 2) is only clamped at 0."""
-    sib = parent - child
-    if cls:
-        return sib.clamp_min_(0.0)
-    y2 = sib[:, 0, 0, 2].clamp_min(0.0)
-    empty = sib[..., 0] <= 0.0
-    sib[..., :2] = torch.where(empty[..., None], torch.zeros_like(sib[..., :2]), sib[..., :2])
-    sib[:, 0, 0, 2] = y2
-    return sib
-
-
-def _impurity(stats: torch.Tensor, kind: str) -> tuple[torch.Tensor, torch.Tensor]:
-    """stats [..., S] -> (impurity, weight)."""
-    if kind == "variance":
-        w = stats[..., 0]
-        mean = stats[..., 1] / w.clamp_min(1e-300)
-        imp = (stats[..., 2] / w.clamp_min(1e-300) - mean * mean).clamp_min(0.0)
-        return torch.where(w > 0, imp, torch.zeros_like(imp)), w
-    w = stats.sum(-1)
-    p = stats / w.clamp_min(1e-300)[..., None]
-    if kind == "gini":
-        imp = 1.0 - (p * p).sum(-1)
-    elif kind == "entropy":
-        imp = -(torch.where(p > 0, p * torch.log2(p.clamp_min(1e-300)), torch.zeros_like(p))).sum(-1)
-    else:
-        raise ValueError(kind)
-    return torch.where(w > 0, imp, torch.zeros_like(imp)), w
-
-
-def _split_bundle_torch(H, kind, cls, nb, bin_ids, fm, min_inst, min_w, min_wfrac, min_w_node=None):
-    """Reference of ``tree_split_kernel``: the per-node decision bundle (fp64
-    [idx | gain | impurity | weight | wL | wR | values]) from histograms [k, F, B, S]."""
-    k = H.shape[0]
-    dev = H.device
-    tot = H[:, 0].sum(1)                                   # [k, S] node stats (feature 0 bins)
-    imp_p, w_p = _impurity(tot, kind)
-    vals = (tot / w_p.clamp_min(1e-300)[:, None]) if cls else (tot[:, 1] / w_p.clamp_min(1e-300))[:, None]
-    # split search: cumulative stats over bins (left = bins <= j)
-    cum = H.cumsum(2)                                      # [k, F, B, S]
-    left = cum[:, :, :-1]
-    right = tot[:, None, None, :] - left
-    W = w_p[:, None, None].clamp_min(1e-300)
-    if cls:
-        iL, wL = _impurity(left, kind)
-        iR, wR = _impurity(right, kind)
-        g = imp_p[:, None, None] - (wL / W) * iL - (wR / W) * iR
-    else:
-        # variance gain from (w, w*y) only: (SyL^2/wL + SyR^2/wR - Sy^2/W) / W
-        wL, wR = left[..., 0], right[..., 0]
-        sL, sR = left[..., 1], right[..., 1]
-        sP = tot[:, 1][:, None, None]
-        g = (sL * sL / wL.clamp_min(1e-300) + sR * sR / wR.clamp_min(1e-300) - sP * sP / W) / W
-    ok = (wL >= min_inst) & (wR >= min_inst)
-    if min_w_node is not None:
-        mw = torch.as_tensor(np.asarray(min_w_node, dtype=np.float64), device=dev)[:, None, None]
-    else:
-        mw = (min_wfrac * w_p)[:, None, None] if min_wfrac > 0.0 else torch.full_like(W, min_w)
-    ok &= (mw <= 0.0) | ((wL >= mw) & (wR >= mw))
-    ok &= bin_ids[None, None, :] < nb[None, :, None]
-    if fm is not None:
-        ok &= torch.from_numpy(fm).to(dev)[:, :, None]
-    g = torch.where(ok, g, torch.full_like(g, -math.inf))
-    best = g.reshape(k, -1).max(1)
-    # global child weights at the chosen split decide which child the next level scans
-    wl_best = wL.reshape(k, -1).gather(1, best.indices[:, None])[:, 0]
-    wr_best = wR.reshape(k, -1).gather(1, best.indices[:, None])[:, 0]
-    return torch.cat([best.indices.to(torch.float64), best.values, imp_p, w_p, wl_best, wr_best, vals.reshape(-1)])
-
-
+# ----------------------------------------------------------------------------- trees
 @dataclass
 class Tree:
     """Flat tree: arrays indexed by Spark node id (1-based; 0 unused)."""
@@ -276,6 +193,32 @@ class Tree:
             imp[self.feature[i]] += self.gain[i] * self.count[i]
         s = imp.sum()
         return imp / s if s > 0 else imp
+
+
+class _Growing:
+    """The node arrays of the trees growing together: ``Tree``'s fields with a leading
+    tree axis, filled level by level."""
+
+    def __init__(self, n_trees: int, max_nodes: int, V: int, splits: list):
+        self.splits = splits
+        self.feature = -np.ones((n_trees, max_nodes), dtype=np.int64)
+        self.split_bin = np.zeros_like(self.feature)
+        self.threshold, self.impurity, self.gain, self.count = (np.zeros((n_trees, max_nodes)) for _ in range(4))
+        self.value = np.zeros((n_trees, max_nodes, V))
+
+    def record_split(self, st, sn, bf, bb, bg) -> None:
+        """Nodes ``sn`` of trees ``st`` split on feature ``bf`` at bin ``bb`` with gain ``bg``."""
+        self.feature[st, sn] = bf
+        self.split_bin[st, sn] = bb
+        self.threshold[st, sn] = [float(self.splits[f_][b_]) for f_, b_ in zip(bf, bb)]
+        self.gain[st, sn] = bg
+
+    def record_nodes(self, st, nid, value, impurity, count) -> None:
+        """Stats of nodes ``nid`` of trees ``st`` (``impurity`` None: filled in later)."""
+        self.value[st, nid] = value
+        if impurity is not None:
+            self.impurity[st, nid] = impurity
+        self.count[st, nid] = count
 
 
 class TreeBuilder:
@@ -355,14 +298,7 @@ class TreeBuilder:
         Tn = len(self.ws)
         F, B, S = self.F, self.B, self.S
         V = S if self.cls else 1
-        max_nodes = 2 ** (self.max_depth + 1)
-        feature = -np.ones((Tn, max_nodes), dtype=np.int64)
-        threshold = np.zeros((Tn, max_nodes))
-        split_bin = np.zeros((Tn, max_nodes), dtype=np.int64)
-        value = np.zeros((Tn, max_nodes, V))
-        impurity = np.zeros((Tn, max_nodes))
-        gain = np.zeros((Tn, max_nodes))
-        count = np.zeros((Tn, max_nodes))
+        nodes = _Growing(Tn, 2 ** (self.max_depth + 1), V, self.splits)
         # one row permutation per tree, tree t at positions [t*n, (t+1)*n); labels and
         # weights travel with the rows in POSITION order (yp[p] belongs to row order[p]),
         # so the histogram kernel streams them instead of gathering a line per row
@@ -393,7 +329,6 @@ class TreeBuilder:
         seg_nid = np.ones(Tn, dtype=np.int64)
         rngs = [np.random.default_rng(sd) for sd in self.seeds]
         nb = torch.tensor([len(s_) for s_ in self.splits], device=dev)
-        bin_ids = torch.arange(B - 1, device=dev)
         root_w = np.zeros(Tn)
         # histogram subtraction: below the root only the globally smaller child of each
         # split is scanned; its sibling is parent - smaller (histograms are additive), which
@@ -406,19 +341,15 @@ class TreeBuilder:
             if k == 0:
                 break
             with trace("tree.hist"):
-                if parent_H is None or not self.hist_subtraction:
-                    H = T.node_hist(self.bins, order, yp, wp, seg_lo, seg_hi, np.arange(k), k, B, S, self.cls,
-                                    ypos=True)
-                    H = H.to(torch.float64).contiguous()
-                    self.comm.all_reduce(H)                       # [k, F, B, S]
-                else:
-                    P = k // 2                                    # segments come as (left, right) pairs
-                    pick_h = 2 * np.arange(P) + small_right.astype(np.int64)
-                    Hs = T.node_hist(self.bins, order, yp, wp, seg_lo[pick_h], seg_hi[pick_h],
-                                     np.arange(P), P, B, S, self.cls, ypos=True)
-                    Hs = Hs.to(torch.float64).contiguous()
-                    self.comm.all_reduce(Hs)
-                    H = T.sibling_hists(Hs, parent_H, small_right, self.cls)
+                subtract = parent_H is not None and self.hist_subtraction
+                # segments come as (left, right) pairs: scan the smaller of each, else every segment
+                scan = 2 * np.arange(k // 2) + small_right.astype(np.int64) if subtract else np.arange(k)
+                H = T.node_hist(self.bins, order, yp, wp, seg_lo[scan], seg_hi[scan], np.arange(len(scan)),
+                                len(scan), B, S, self.cls, ypos=True)
+                H = H.to(torch.float64).contiguous()
+                self.comm.all_reduce(H)                           # [k or k / 2, F, B, S]
+                if subtract:
+                    H = T.sibling_hists(H, parent_H, small_right, self.cls)
             with trace("tree.split"):
                 fm = None
                 if self.ffrac < 1.0:
@@ -434,11 +365,7 @@ class TreeBuilder:
                 # minWeightFractionPerNode), below it the absolute value that gave, per tree
                 mw_frac = self.min_wfrac if depth == 0 else 0.0
                 mw_node = (self.min_wfrac * root_w[seg_tree]) if (depth > 0 and self.min_wfrac > 0.0) else None
-                if H.is_cuda:
-                    bundle_t = T.best_splits(H, nb, fm, self.kind, self.min_inst, 0.0, mw_frac, mw_node)
-                else:
-                    bundle_t = _split_bundle_torch(H, self.kind, self.cls, nb, bin_ids, fm, self.min_inst, 0.0,
-                                                   mw_frac, mw_node)
+                bundle_t = T.best_splits(H, nb, fm, self.kind, self.min_inst, 0.0, mw_frac, mw_node)
                 # ONE device->host copy of every per-node decision input
                 bundle = bundle_t.cpu().numpy()
                 bi = bundle[:k].astype(np.int64)
@@ -456,9 +383,10 @@ class TreeBuilder:
                 # one routing pass applies the leaf values / sums the REG w*y^2 -- no
                 # partition, no histogram and no split search for the last level
                 with trace("tree.final_level"):
-                    self._final_level(H, do_split, bf, bb, bg, seg_lo, seg_hi, seg_tree, seg_nid, order, yp, wp,
-                                      leaf_acc, leaf_scale, value, impurity, count, feature, split_bin, threshold,
-                                      gain)
+                    idx = np.nonzero(do_split)[0]
+                    self._final_level(nodes, H, idx, (bf[idx], bb[idx], bg[idx]),
+                                      (seg_lo[idx], seg_hi[idx], seg_tree[idx], seg_nid[idx]), (order, yp, wp),
+                                      leaf_acc, leaf_scale)
                 do_split = np.zeros_like(do_split)            # nothing left to grow
             if do_split.any():
                 # the partition is launched first: the tree bookkeeping and the leaf
@@ -467,97 +395,70 @@ class TreeBuilder:
                     st, sn = seg_tree[do_split], seg_nid[do_split]
                     s_lo, s_hi = seg_lo[do_split], seg_hi[do_split]
                     pay = (yp,) if wp is None else (yp, wp)
-                    if pingpong:
-                        pout = (y_sp,) if wp is None else (y_sp, w_sp)
-                        new_order, nleft = T.partition(self.bins, order, s_lo, s_hi, bf[do_split], bb[do_split],
-                                                       bins_t=self.bins_t, out=spare, payload=pay, payload_out=pout)
-                        spare, order = order, new_order
-                        y_sp, yp = yp, y_sp
-                        w_sp, wp = wp, w_sp
-                    else:
-                        pout = tuple(t.clone() for t in pay)
-                        order, nleft = T.partition(self.bins, order, s_lo, s_hi, bf[do_split], bb[do_split],
-                                                   bins_t=self.bins_t, payload=pay, payload_out=pout)
-                        yp, wp = pout[0], (pout[1] if len(pout) > 1 else None)
+                    pout = (y_sp, w_sp)[:len(pay)] if pingpong else tuple(t.clone() for t in pay)
+                    new_order, nleft = T.partition(self.bins, order, s_lo, s_hi, bf[do_split], bb[do_split],
+                                                   bins_t=self.bins_t, out=spare, payload=pay, payload_out=pout)
+                    if pingpong:                              # the buffers just read are the next spares
+                        spare, y_sp, w_sp = order, yp, wp
+                    order, yp, wp = new_order, pout[0], (pout[1] if len(pout) > 1 else None)
                     # integer gather (a boolean mask index would sync on the device-side nonzero)
                     parent_H = H.index_select(0, N.upload(np.nonzero(do_split)[0], dev))
                     small_right = (wr_np < wl_np)[do_split]
-            value[seg_tree, seg_nid] = vals_np
-            impurity[seg_tree, seg_nid] = imp_np
-            count[seg_tree, seg_nid] = w_np
+            nodes.record_nodes(seg_tree, seg_nid, vals_np, imp_np, w_np)
             if leaf_acc is not None and is_leaf.any() and not self.defer_leaves:
                 with trace("tree.leaf_apply"):          # finished segments: rows in the pre-split order
                     lf = is_leaf
-                    T.leaf_apply(old_order, seg_lo[lf], seg_hi[lf], value[seg_tree[lf], seg_nid[lf], 0] * leaf_scale,
-                                 leaf_acc)
+                    T.leaf_apply(old_order, seg_lo[lf], seg_hi[lf],
+                                 nodes.value[seg_tree[lf], seg_nid[lf], 0] * leaf_scale, leaf_acc)
             if not do_split.any():
                 break
             with trace("tree.partition"):
-                feature[st, sn] = bf[do_split]
-                split_bin[st, sn] = bb[do_split]
-                threshold[st, sn] = [float(self.splits[f_][b_]) for f_, b_ in zip(bf[do_split], bb[do_split])]
-                gain[st, sn] = bg[do_split]
+                nodes.record_split(st, sn, bf[do_split], bb[do_split], bg[do_split])
                 mid = s_lo + nleft.cpu().numpy().astype(np.int64)
                 seg_lo = np.stack([s_lo, mid], 1).reshape(-1)
                 seg_hi = np.stack([mid, s_hi], 1).reshape(-1)
                 seg_tree = np.repeat(st, 2)
                 seg_nid = np.stack([2 * sn, 2 * sn + 1], 1).reshape(-1)
             # empty local segments still participate (other ranks may have rows there)
-        return [Tree(feature[t], threshold[t], split_bin[t], value[t], impurity[t], gain[t], count[t], F)
-                for t in range(Tn)]
+        return [Tree(nodes.feature[t], nodes.threshold[t], nodes.split_bin[t], nodes.value[t], nodes.impurity[t],
+                     nodes.gain[t], nodes.count[t], F) for t in range(Tn)]
 
-    def _final_level(self, H, do_split, bf, bb, bg, seg_lo, seg_hi, seg_tree, seg_nid, order, yp, wp, leaf_acc,
-                     leaf_scale, value, impurity, count, feature, split_bin, threshold, gain):
+    def _final_level(self, nodes, H, idx, split, seg, rows, leaf_acc, leaf_scale):
+        """Segments ``idx`` of the level (histograms H) split into leaves: ``split`` = their
+        (feature, bin, gain), ``seg`` = their (lo, hi, tree, node id), ``rows`` = (order, y, w)."""
         dev = H.device
-        idx = np.nonzero(do_split)[0]
         P = len(idx)
-        st, sn = seg_tree[idx], seg_nid[idx]
-        feature[st, sn] = bf[idx]
-        split_bin[st, sn] = bb[idx]
-        threshold[st, sn] = [float(self.splits[f_][b_]) for f_, b_ in zip(bf[idx], bb[idx])]
-        gain[st, sn] = bg[idx]
-        idx_d, bf_d, bb_d = (N.upload(a.astype(np.int64), dev) for a in (idx, bf[idx], bb[idx]))
+        bf, bb, bg = split
+        s_lo, s_hi, st, sn = seg
+        order, yp, wp = rows
+        nodes.record_split(st, sn, bf, bb, bg)
+        idx_d, bf_d, bb_d = (N.upload(a.astype(np.int64), dev) for a in (idx, bf, bb))
         Hp = H.index_select(0, idx_d)                                        # [P, F, B, S]
         ar = torch.arange(P, device=dev)
         left = Hp[ar, bf_d].cumsum(1)[ar, bb_d]                               # [P, S]
         tot = Hp[:, 0].sum(1)                                                 # node totals (feature 0)
         child = torch.stack([left, tot - left], 1).cpu().numpy()              # [P, 2, S]
         w_ch = child[..., :].sum(-1) if self.cls else child[..., 0]
-        V = self.S if self.cls else 1
+        nid = np.stack([2 * sn, 2 * sn + 1], 1)                               # [P, 2] children
         if self.cls:
             vals = child / np.maximum(w_ch, 1e-300)[..., None]
         else:
             vals = (child[..., 1] / np.maximum(w_ch, 1e-300))[..., None]
-        s_lo, s_hi = seg_lo[idx], seg_hi[idx]
-        if self.defer_leaves:            # rows are routed (and y^2 summed) by the caller's leaf pass
-            for side in (0, 1):
-                nid = 2 * sn + side
-                value[st, nid] = vals[:, side].reshape(P, V)
-                count[st, nid] = w_ch[:, side]
-            if not self.cls:
-                self.pending_y2 = (np.stack([2 * sn, 2 * sn + 1], 1), child[..., 0], child[..., 1])
-            else:
-                imp, _ = _impurity(torch.from_numpy(child), self.kind)
-                for side in (0, 1):
-                    impurity[st, 2 * sn + side] = imp.numpy()[:, side]
-            return
-        y2 = T.final_level(self.bins, order, s_lo, s_hi, bf[idx], bb[idx], vals[:, 0, 0] * leaf_scale,
-                           vals[:, 1, 0] * leaf_scale, yp, wp, leaf_acc, need_y2=not self.cls,
-                           bins_t=self.bins_t) if (leaf_acc is not None or not self.cls) else None
+        if not self.defer_leaves and (leaf_acc is not None or not self.cls):
+            y2 = T.final_level(self.bins, order, s_lo, s_hi, bf, bb, vals[:, 0, 0] * leaf_scale,
+                               vals[:, 1, 0] * leaf_scale, yp, wp, leaf_acc, need_y2=not self.cls,
+                               bins_t=self.bins_t)
         if self.cls:
-            imp, _ = _impurity(torch.from_numpy(child), self.kind)
+            imp = T._impurity(torch.from_numpy(child), self.kind)[0].numpy()
+        elif self.defer_leaves:          # rows are routed (and y^2 summed) by the caller's leaf pass:
+            imp = None                   # complete_final() fills the impurities in
+            self.pending_y2 = (nid, child[..., 0], child[..., 1])
         else:
             y2 = y2.contiguous()
             self.comm.all_reduce(y2)
             stats = np.concatenate([child[..., :2], y2.cpu().numpy()[..., None]], -1)   # [P, 2, 3]
-            imp, _ = _impurity(torch.from_numpy(stats), self.kind)
-        imp = imp.numpy()
-        for side in (0, 1):
-            nid = 2 * sn + side
-            value[st, nid] = vals[:, side].reshape(P, V)
-            impurity[st, nid] = imp[:, side]
-            count[st, nid] = w_ch[:, side]
-
+            imp = T._impurity(torch.from_numpy(stats), self.kind)[0].numpy()
+        nodes.record_nodes(st[:, None], nid, vals, imp, w_ch)
 
     def complete_final(self, tree: "Tree", y2_leaves) -> None:
         """defer_leaves: the impurities of the last level's children from the leaf pass's
@@ -567,7 +468,7 @@ class TreeBuilder:
         nid, w, wy = self.pending_y2
         y2 = np.asarray(y2_leaves, dtype=np.float64)[nid - (1 << self.max_depth)]
         stats = np.stack([w, wy, y2], -1)                                  # [P, 2, 3]
-        imp, _ = _impurity(torch.from_numpy(stats), self.kind)
+        imp, _ = T._impurity(torch.from_numpy(stats), self.kind)
         tree.impurity[nid] = imp.numpy()
         self.pending_y2 = None
 
@@ -582,7 +483,7 @@ class Ensemble:
     losses: list = field(default_factory=list)
 
 
-def subsample_weights(n_local, rows: torch.Tensor, rate: float, seed: int, bootstrap: bool) -> torch.Tensor | None:
+def subsample_weights(rows: torch.Tensor, rate: float, seed: int, bootstrap: bool) -> torch.Tensor | None:
     if bootstrap:
         return sampling.poisson_counts(rows, seed, rate).to(torch.float32)
     if rate < 1.0:
@@ -628,7 +529,7 @@ def fit_gbt(comm, bins, splits, y: torch.Tensor, w, loss: str = "logistic", max_
         progress.iteration(m, max_iter)
         sw = w
         if subsampling_rate < 1.0 and rows is not None:
-            sub = subsample_weights(None, rows, subsampling_rate, seed + m, False)
+            sub = subsample_weights(rows, subsampling_rate, seed + m, False)
             sw = sub if w is None else w * sub
         tb = TreeBuilder(comm, bins, splits, target, sw, "variance", 1, max_depth, min_instances,
                          min_info_gain, feature_fraction, seed + m, bins_t=bins_t,
@@ -685,20 +586,11 @@ def fit_forest(comm, bins, splits, y, w, num_trees: int, impurity: str, num_clas
     with trace("forest.weights"):
         if rows.is_cuda and (bootstrap or subsampling_rate < 1.0):
             # every tree's bootstrap / subsample weights in one kernel (same draws)
-            seeds = np.array([(seed * 7919 + t) & 0xFFFFFFFF for t in range(num_trees)], dtype=np.uint32)
-            table = sampling.poisson_table(subsampling_rate, rows.device) if bootstrap else None
-            wf = None if w is None else w.to(rows.device, torch.float32).contiguous()
-            out = torch.empty((num_trees, rows.shape[0]), dtype=torch.float32, device=rows.device)
-            r64 = rows.to(torch.int64).contiguous()
-            N.check(N.kernels().o3s_forest_weights(r64.data_ptr(), r64.shape[0],
-                                                   N.upload(seeds.view(np.int32), rows.device).data_ptr(),
-                                                   num_trees, N.ptr(table), 0 if table is None else table.numel(),
-                                                   float(subsampling_rate), N.ptr(wf), out.data_ptr(),
-                                                   N.stream_of(out)), "forest_weights")
-            ws = list(out)
+            seeds = [(seed * 7919 + t) & 0xFFFFFFFF for t in range(num_trees)]
+            ws = list(T.forest_weights(rows, seeds, subsampling_rate, bootstrap, w))
         else:
             for t in range(num_trees):
-                sw = subsample_weights(None, rows, subsampling_rate, seed * 7919 + t, bootstrap)
+                sw = subsample_weights(rows, subsampling_rate, seed * 7919 + t, bootstrap)
                 if w is not None:
                     sw = w if sw is None else w * sw
                 ws.append(sw)

@@ -1,24 +1,56 @@
 """Tree histogram op: gfx950 kernel (csrc/trees.hip) with a PyTorch reference."""
 from __future__ import annotations
 
+import math
 import os
 
 import numpy as np
 import torch
 
 from . import _native as N
+from . import sampling
 
 
-def _host(x):
-    """int64 numpy view of a small index array given as numpy or a (device) tensor."""
-    import numpy as np
+def _host(x, dtype=np.int64):
+    """numpy copy (int64: indices) of a small array given as numpy or a (device) tensor."""
     if isinstance(x, torch.Tensor):
-        return x.detach().to("cpu", torch.int64).numpy()
-    return np.asarray(x, dtype=np.int64)
+        x = x.detach().cpu().numpy()
+    return np.asarray(x, dtype=dtype)
 
 
 def _dev(x, dev):
     return x.to(dev) if isinstance(x, torch.Tensor) else N.upload(_host(x), dev)
+
+
+def _plan_items(lo, hi, chunk: int):
+    """Segments [lo, hi) (host int64) cut into work items of <= ``chunk`` rows: per item its
+    segment and bounds (seg_of, it_lo, it_hi), per segment its first item and item count
+    (first, n_it).  The ONE plan: these bounds fix the fp32 partials and the fp64 sum order."""
+    n_it = (np.maximum(hi - lo, 0) + chunk - 1) // chunk
+    first = np.cumsum(n_it) - n_it
+    seg_of = np.repeat(np.arange(len(lo)), n_it)
+    it_lo = lo[seg_of] + (np.arange(len(seg_of)) - first[seg_of]) * chunk
+    it_hi = np.minimum(it_lo + chunk, hi[seg_of])
+    return seg_of, it_lo, it_hi, first, n_it
+
+
+def _range_sums(src: torch.Tensor, C: int, r_lo: torch.Tensor, r_cnt: torch.Tensor, out: torch.Tensor, st) -> None:
+    """out[i] = fp64 sum, in row order, of the rows [r_lo[i], r_lo[i] + r_cnt[i]) of ``src``
+    ([rows, C], fp32 or fp64): ``slab_range_sum_kernel``, <= 65535 ranges per launch."""
+    n = out.shape[0]
+    for a in range(0, n, 65535):
+        b = min(a + 65535, n)
+        N.check(N.kernels().o3s_slab_range_sum(src.data_ptr(), int(src.dtype == torch.float64), C, r_lo[a:].data_ptr(),
+                                               r_cnt[a:].data_ptr(), b - a, out[a:].data_ptr(), st), "slab_range_sum")
+
+
+def _bins_src(bins, bins_t):     # (matrix, row stride, column stride) of the per-row feature reads
+    return (bins_t, 1, bins.shape[0]) if bins_t is not None else (bins, bins.shape[1], 1)
+
+
+def _check_target(target: torch.Tensor | None, n: int) -> None:
+    if target is not None and (target.dtype != torch.float32 or target.numel() != n or not target.is_contiguous()):
+        raise ValueError("target must be a contiguous fp32 [n] tensor")
 
 
 def hist_kernel_ok(bins: torch.Tensor, B: int, S: int, cls: bool) -> bool:
@@ -29,6 +61,31 @@ def hist_kernel_ok(bins: torch.Tensor, B: int, S: int, cls: bool) -> bool:
     while fp < F and fp < 64:
         fp <<= 1
     return N.kernels().o3s_tree_hist_lds(fp, B, S, int(cls)) > 0
+
+
+def bin_block(X: torch.Tensor, tht, Tp, out: torch.Tensor, out_t: torch.Tensor | None, ldt: int) -> None:
+    """``bin_features_kernel`` on a row block X (fp32 / bf16; thresholds ``tht`` [F, Tp]): bins
+    into ``out`` and, with ``out_t`` (row length ``ldt``), feature-major in the same pass."""
+    n, F = X.shape
+    N.check(N.kernels().o3s_bin_features2(X.data_ptr(), int(X.dtype == torch.bfloat16), n, X.stride(0), F,
+                                          tht.data_ptr(), Tp, out.data_ptr(), N.ptr(out_t), ldt, N.stream_of(X)),
+            "bin_features")
+
+
+def forest_weights(rows: torch.Tensor, seeds, rate: float, bootstrap: bool, w: torch.Tensor | None) -> torch.Tensor:
+    """fp32 [len(seeds), n]: ``w`` times every tree's bootstrap / subsample weights in ONE
+    launch (``forest_weights_kernel``): ``models.trees.subsample_weights``' draws per seed."""
+    dev = rows.device
+    seeds = np.asarray(seeds, dtype=np.uint32)
+    table = sampling.poisson_table(rate, dev) if bootstrap else None
+    wf = None if w is None else w.to(dev, torch.float32).contiguous()
+    out = torch.empty((len(seeds), rows.shape[0]), dtype=torch.float32, device=dev)
+    r64 = rows.to(torch.int64).contiguous()
+    N.check(N.kernels().o3s_forest_weights(r64.data_ptr(), r64.shape[0], N.upload(seeds.view(np.int32), dev).data_ptr(),
+                                           len(seeds), N.ptr(table), 0 if table is None else table.numel(),
+                                           float(rate), N.ptr(wf), out.data_ptr(), N.stream_of(out)),
+            "forest_weights")
+    return out
 
 
 # row-major bins -> the feature-major copy written in the same pass by the binning kernel
@@ -83,21 +140,15 @@ def partition(bins: torch.Tensor, order: torch.Tensor, s_lo: torch.Tensor, s_hi:
         dv = bins.device
         return partition_torch(bins, order, _dev(s_lo, dv), _dev(s_hi, dv), _dev(s_feat, dv), _dev(s_bin, dv),
                                out=out, payload=payload, payload_out=payload_out)
-    import numpy as np
     dev = bins.device
-    F = bins.shape[1]
     # work items planned on the host (segment bounds are tiny) and uploaded in one copy
     lo, hi = _host(s_lo), _host(s_hi)
     nseg = len(lo)
-    n_it = (np.maximum(hi - lo, 0) + chunk - 1) // chunk
-    first = np.cumsum(n_it) - n_it
-    n_items = int(n_it.sum())
+    seg_of, it_lo_h, it_hi_h, first, _ = _plan_items(lo, hi, chunk)
+    n_items = len(seg_of)
     new_order = order.clone() if out is None else out
     if n_items == 0:
         return new_order, torch.zeros(nseg, dtype=torch.int64, device=dev)
-    seg_of = np.repeat(np.arange(nseg), n_it)
-    it_lo_h = lo[seg_of] + (np.arange(n_items) - first[seg_of]) * chunk
-    it_hi_h = np.minimum(it_lo_h + chunk, hi[seg_of])
     seg_first = np.append(first, n_items)
     fb = np.concatenate([_host(s_feat).astype(np.int32)[seg_of], _host(s_bin).astype(np.int32)[seg_of]])
     i64, i32 = N.upload_many(dev, np.concatenate([it_lo_h, it_hi_h, seg_first, lo]).astype(np.int64), fb)
@@ -110,7 +161,7 @@ def partition(bins: torch.Tensor, order: torch.Tensor, s_lo: torch.Tensor, s_hi:
     flags = torch.empty(order.shape[0], dtype=torch.uint8, device=dev)
     lib = N.kernels()
     st = N.stream_of(bins)
-    src, rs, cs = (bins_t, 1, bins.shape[0]) if bins_t is not None else (bins, F, 1)
+    src, rs, cs = _bins_src(bins, bins_t)
     N.check(lib.o3s_tree_partition(src.data_ptr(), rs, cs, order.data_ptr(), None, it_lo.data_ptr(), it_hi.data_ptr(),
                                    it_feat.data_ptr(), it_bin.data_ptr(), it_left.data_ptr(), None, None,
                                    flags.data_ptr(), n_items, 0, None, None, None, None, st), "tree_part_count")
@@ -138,65 +189,63 @@ def final_level(bins: torch.Tensor, order: torch.Tensor, s_lo, s_hi, s_feat, s_b
     (``vl`` / ``vr`` per segment) and, with ``need_y2``, the children's sums of w*y^2
     (fp64 [nseg, 2]: left, right; y / w in position order) are returned, else None.
 
-    GPU: ``tree_final_level_kernel`` + ordered fp64 range sums; CPU: torch."""
+    GPU: ``tree_final_level_kernel`` + ordered fp64 range sums; CPU: ``final_level_torch``."""
+    if not (bins.is_cuda and order.dtype == torch.int32):
+        return final_level_torch(bins, order, s_lo, s_hi, s_feat, s_bin, vl, vr, y, w, acc, need_y2)
     lo, hi = _host(s_lo), _host(s_hi)
     nseg = len(lo)
     dev = bins.device
-    vl = np.asarray(vl, dtype=np.float64)
-    vr = np.asarray(vr, dtype=np.float64)
-    if nseg == 0:
-        return torch.zeros((0, 2), dtype=torch.float64, device=dev) if need_y2 else None
-    if not (bins.is_cuda and order.dtype == torch.int32):
-        F = bins.shape[1]
-        lens = np.maximum(hi - lo, 0)
-        sid = np.repeat(np.arange(nseg), lens)
-        pos = torch.from_numpy(np.concatenate([np.arange(a, b) for a, b in zip(lo, hi)]) if lens.sum()
-                               else np.zeros(0, dtype=np.int64)).to(dev)
-        rows = order[pos].long()
-        fe = torch.from_numpy(_host(s_feat)[sid]).to(dev)
-        bb = torch.from_numpy(_host(s_bin)[sid]).to(dev)
-        left = bins.view(-1)[rows * F + fe].to(torch.int64) <= bb
-        sid_t = torch.from_numpy(sid).to(dev)
-        if acc is not None:
-            v = torch.where(left, torch.from_numpy(vl[sid]).to(dev), torch.from_numpy(vr[sid]).to(dev))
-            acc.index_add_(0, rows.to(acc.device), v.to(acc.dtype))
-        if not need_y2:
-            return None
-        yy = y[pos].to(torch.float64)
-        ww = torch.ones_like(yy) if w is None else w[pos].to(torch.float64)
-        out = torch.zeros((nseg, 2), dtype=torch.float64, device=dev)
-        out.view(-1).index_add_(0, sid_t * 2 + (~left).long(), ww * yy * yy)
-        return out
-    n_it = (np.maximum(hi - lo, 0) + chunk - 1) // chunk
-    first = np.cumsum(n_it) - n_it
-    n_items = int(n_it.sum())
+    vl, vr = np.asarray(vl, dtype=np.float64), np.asarray(vr, dtype=np.float64)
+    seg_of, it_lo, it_hi, first, n_it = _plan_items(lo, hi, chunk)
+    n_items = len(seg_of)
     if n_items == 0:
         return torch.zeros((nseg, 2), dtype=torch.float64, device=dev) if need_y2 else None
-    seg_of = np.repeat(np.arange(nseg), n_it)
-    it_lo = lo[seg_of] + (np.arange(n_items) - first[seg_of]) * chunk
-    it_hi = np.minimum(it_lo + chunk, hi[seg_of])
     fb = np.concatenate([_host(s_feat).astype(np.int32)[seg_of], _host(s_bin).astype(np.int32)[seg_of]])
-    r_lo, r_cnt = first, n_it
-    i64, i32, f64 = N.upload_many(dev, np.concatenate([it_lo, it_hi, r_lo, r_cnt]).astype(np.int64), fb,
+    i64, i32, f64 = N.upload_many(dev, np.concatenate([it_lo, it_hi, first, n_it]).astype(np.int64), fb,
                                   np.concatenate([vl[seg_of], vr[seg_of]]))
     part = torch.empty((n_items, 2), dtype=torch.float32, device=dev) if need_y2 else None
     yf = y.to(torch.float32).contiguous() if need_y2 else None
     wf = None if (w is None or not need_y2) else w.to(torch.float32).contiguous()
-    src, rs, cs = (bins_t, 1, bins.shape[0]) if bins_t is not None else (bins, bins.shape[1], 1)
-    lib = N.kernels()
+    src, rs, cs = _bins_src(bins, bins_t)
     st = N.stream_of(bins)
-    N.check(lib.o3s_tree_final_level(src.data_ptr(), rs, cs, order.data_ptr(), i64[:n_items].data_ptr(),
-                                     i64[n_items:2 * n_items].data_ptr(), i32[:n_items].data_ptr(),
-                                     i32[n_items:].data_ptr(), f64[:n_items].data_ptr(), f64[n_items:].data_ptr(),
-                                     N.ptr(yf), N.ptr(wf), N.ptr(acc), N.ptr(part), n_items, st), "tree_final_level")
+    N.check(N.kernels().o3s_tree_final_level(src.data_ptr(), rs, cs, order.data_ptr(), i64[:n_items].data_ptr(),
+                                             i64[n_items:2 * n_items].data_ptr(), i32[:n_items].data_ptr(),
+                                             i32[n_items:].data_ptr(), f64[:n_items].data_ptr(),
+                                             f64[n_items:].data_ptr(), N.ptr(yf), N.ptr(wf), N.ptr(acc), N.ptr(part),
+                                             n_items, st), "tree_final_level")
     if not need_y2:
         return None
     out = torch.empty((nseg, 2), dtype=torch.float64, device=dev)
-    rl, rc = i64[2 * n_items:2 * n_items + nseg], i64[2 * n_items + nseg:]
-    for a in range(0, nseg, 65535):                           # item partials summed per segment, in order
-        b = min(a + 65535, nseg)
-        N.check(lib.o3s_slab_range_sum(part.data_ptr(), 0, 2, rl[a:].data_ptr(), rc[a:].data_ptr(), b - a,
-                                       out[a:].data_ptr(), st), "slab_range_sum")
+    # item partials summed per segment, in order
+    _range_sums(part, 2, i64[2 * n_items:2 * n_items + nseg], i64[2 * n_items + nseg:], out, st)
+    return out
+
+
+def final_level_torch(bins, order, s_lo, s_hi, s_feat, s_bin, vl, vr, y, w, acc, need_y2):
+    """Reference of ``final_level``: fp64 gathers and scatter-adds over the segments' rows."""
+    lo, hi = _host(s_lo), _host(s_hi)
+    nseg = len(lo)
+    dev = bins.device
+    vl, vr = np.asarray(vl, dtype=np.float64), np.asarray(vr, dtype=np.float64)
+    F = bins.shape[1]
+    lens = np.maximum(hi - lo, 0)
+    sid = np.repeat(np.arange(nseg), lens)
+    pos = torch.from_numpy(np.concatenate([np.arange(a, b) for a, b in zip(lo, hi)]) if lens.sum()
+                           else np.zeros(0, dtype=np.int64)).to(dev)
+    rows = order[pos].long()
+    fe = torch.from_numpy(_host(s_feat)[sid]).to(dev)
+    bb = torch.from_numpy(_host(s_bin)[sid]).to(dev)
+    left = bins.view(-1)[rows * F + fe].to(torch.int64) <= bb
+    sid_t = torch.from_numpy(sid).to(dev)
+    if acc is not None:
+        v = torch.where(left, torch.from_numpy(vl[sid]).to(dev), torch.from_numpy(vr[sid]).to(dev))
+        acc.index_add_(0, rows.to(acc.device), v.to(acc.dtype))
+    if not need_y2:
+        return None
+    yy = y[pos].to(torch.float64)
+    ww = torch.ones_like(yy) if w is None else w[pos].to(torch.float64)
+    out = torch.zeros((nseg, 2), dtype=torch.float64, device=dev)
+    out.view(-1).index_add_(0, sid_t * 2 + (~left).long(), ww * yy * yy)
     return out
 
 
@@ -204,35 +253,28 @@ def leaf_apply(order: torch.Tensor, seg_lo: torch.Tensor, seg_hi: torch.Tensor, 
                acc: torch.Tensor, chunk: int = 1 << 14) -> None:
     """acc[order[p]] += seg_val[s] for every position p of segment s (fp64 acc).
 
-    GPU: ``tree_leaf_apply_kernel`` over <= chunk-row items planned on the host; CPU: torch."""
-    import numpy as np
-    if len(seg_lo) == 0:
-        return
-    dev = acc.device
-    lo, hi = _host(seg_lo), _host(seg_hi)
-    val = seg_val.detach().to("cpu", torch.float64).numpy() if isinstance(seg_val, torch.Tensor) \
-        else np.asarray(seg_val, dtype=np.float64)
-    lens = np.maximum(hi - lo, 0)
+    GPU: ``tree_leaf_apply_kernel`` over <= chunk-row items planned on the host; CPU: ``leaf_apply_torch``."""
     if not (acc.is_cuda and order.dtype == torch.int32 and acc.dtype == torch.float64):
-        if lens.sum() == 0:
-            return
-        pos = torch.from_numpy(np.concatenate([np.arange(a, b) for a, b in zip(lo, hi)])).to(order.device)
-        v = torch.from_numpy(np.repeat(val, lens)).to(acc.device, acc.dtype)
-        acc.index_add_(0, order[pos].long().to(acc.device), v)
-        return
-    n_it = (lens + chunk - 1) // chunk
-    first = np.cumsum(n_it) - n_it
-    n_items = int(n_it.sum())
+        return leaf_apply_torch(order, seg_lo, seg_hi, seg_val, acc)
+    seg_of, it_lo, it_hi, _, _ = _plan_items(_host(seg_lo), _host(seg_hi), chunk)
+    n_items = len(seg_of)
     if n_items == 0:
         return
-    seg_of = np.repeat(np.arange(len(lo)), n_it)
-    it_lo = lo[seg_of] + (np.arange(n_items) - first[seg_of]) * chunk
-    it_hi = np.minimum(it_lo + chunk, hi[seg_of])
-    i64, fv = N.upload_many(dev, np.concatenate([it_lo, it_hi]).astype(np.int64),
-                            np.ascontiguousarray(val[seg_of], dtype=np.float64))
+    i64, fv = N.upload_many(acc.device, np.concatenate([it_lo, it_hi]).astype(np.int64),
+                            np.ascontiguousarray(_host(seg_val, np.float64)[seg_of], dtype=np.float64))
     N.check(N.kernels().o3s_tree_leaf_apply(order.data_ptr(), i64[:n_items].data_ptr(), i64[n_items:].data_ptr(),
                                             fv.data_ptr(), n_items, acc.data_ptr(), N.stream_of(acc)),
             "tree_leaf_apply")
+
+
+def leaf_apply_torch(order, seg_lo, seg_hi, seg_val, acc) -> None:
+    lo, hi = _host(seg_lo), _host(seg_hi)
+    lens = np.maximum(hi - lo, 0)
+    if lens.sum() == 0:
+        return
+    pos = torch.from_numpy(np.concatenate([np.arange(a, b) for a, b in zip(lo, hi)])).to(order.device)
+    v = torch.from_numpy(np.repeat(_host(seg_val, np.float64), lens)).to(acc.device, acc.dtype)
+    acc.index_add_(0, order[pos].long().to(acc.device), v)
 
 
 _KINDS = {"variance": 0, "gini": 1, "entropy": 2}
@@ -263,18 +305,22 @@ def gbt_grad_loss(loss: str, yy: torch.Tensor, Fm: torch.Tensor, w: torch.Tensor
     """One boosting epilogue pass: returns fp64 [sum loss*w, sum w, sum loss*w_val,
     sum w_val] over the local rows and (``target`` given, fp32) writes the residuals of
     the next tree into it.  GPU: ``gbt_grad_loss_kernel`` (one fused pass, fixed-grid
-    partial sums); CPU: the torch reference."""
+    partial sums); CPU: ``gbt_grad_loss_torch``."""
     n = yy.shape[0]
+    if not (yy.is_cuda and n > 0):
+        return gbt_grad_loss_torch(loss, yy, Fm, w, w_val, target)
+    f64 = [None if t is None else t.to(torch.float64).contiguous() for t in (yy, Fm, w, w_val)]
+    nb = int(min(2048, max(1, (n + 255) // 256)))
+    part = torch.empty((nb, 4), dtype=torch.float64, device=yy.device)
+    _check_target(target, n)
+    N.check(N.kernels().o3s_gbt_grad_loss(*(N.ptr(t) for t in f64), n, _GBT_LOSS[loss], N.ptr(target),
+                                          part.data_ptr(), nb, N.stream_of(yy)), "gbt_grad_loss")
+    return part.sum(0)
+
+
+def gbt_grad_loss_torch(loss, yy, Fm, w, w_val, target=None):
+    """Reference of ``gbt_grad_loss`` (fp64 torch reductions)."""
     dev = yy.device
-    if yy.is_cuda and n > 0:
-        f64 = [None if t is None else t.to(torch.float64).contiguous() for t in (yy, Fm, w, w_val)]
-        nb = int(min(2048, max(1, (n + 255) // 256)))
-        part = torch.empty((nb, 4), dtype=torch.float64, device=dev)
-        if target is not None and (target.dtype != torch.float32 or target.numel() != n or not target.is_contiguous()):
-            raise ValueError("target must be a contiguous fp32 [n] tensor")
-        N.check(N.kernels().o3s_gbt_grad_loss(*(N.ptr(t) for t in f64), n, _GBT_LOSS[loss], N.ptr(target),
-                                              part.data_ptr(), nb, N.stream_of(yy)), "gbt_grad_loss")
-        return part.sum(0)
     pl = gbt_point_loss(loss, yy.double(), Fm.double())
     wt = torch.ones_like(pl) if w is None else w.double()
     out = [(pl * wt).sum(), wt.sum()]
@@ -310,37 +356,44 @@ def gbt_leaf_pass(bins: torch.Tensor, feature, split_bin, value, scale: float, d
     returned, ``target`` (fp32, optional) receives the next tree's residuals, and with
     ``need_y2`` the sums of wt*y^2 of the leaves at depth ``depth`` (fp64 [2^depth], y =
     the residual this tree was fit to: yy for the first tree, else the loss gradient at
-    the pre-update Fm) -- the last level's children impurities.  CPU: torch."""
+    the pre-update Fm) -- the last level's children impurities.  CPU: ``gbt_leaf_pass_torch``."""
     n, F = bins.shape
     dev = bins.device
+    if not (bins.is_cuda and n > 0):
+        return gbt_leaf_pass_torch(bins, feature, split_bin, value, scale, depth, loss, yy, Fm, wt, wd, wv, first,
+                                   target, need_y2)
     fb, val = tree_node_arrays(feature, split_bin, value, scale)
-    nodes = len(fb)
     L = 1 << depth
-    if bins.is_cuda and n > 0:
-        f64 = [None if t is None else t.to(torch.float64).contiguous() for t in (wd, wv)]
-        wt32 = None if wt is None else wt.to(torch.float32).contiguous()
-        if target is not None and (target.dtype != torch.float32 or target.numel() != n or not target.is_contiguous()):
-            raise ValueError("target must be a contiguous fp32 [n] tensor")
-        if not (yy.dtype == torch.float64 and Fm.dtype == torch.float64 and yy.is_contiguous() and Fm.is_contiguous()):
-            raise ValueError("yy / Fm must be contiguous fp64")
-        grid = int(max(1, min(N.num_cus(dev) * LEAF_BLOCKS_PER_CU, (n + 255) // 256)))
-        part = torch.empty((grid, 4), dtype=torch.float64, device=dev)
-        slab = torch.empty((grid * 4, L), dtype=torch.float32, device=dev) if need_y2 else None   # a row per wave
-        fb_d, val_d = N.upload_many(dev, fb, val)
-        lib = N.kernels()
-        N.check(lib.o3s_gbt_leaf_pass(bins.data_ptr(), n, F, fb_d.data_ptr(), nodes, val_d.data_ptr(), depth,
-                                      yy.data_ptr(), Fm.data_ptr(), N.ptr(wt32), N.ptr(f64[0]), N.ptr(f64[1]),
-                                      _GBT_LOSS[loss], int(first), N.ptr(target), part.data_ptr(), N.ptr(slab),
-                                      grid, N.stream_of(Fm)), "gbt_leaf_pass")
-        y2 = None
-        if need_y2:
-            y2 = torch.empty((1, L), dtype=torch.float64, device=dev)
-            lo, cnt = N.upload_many(dev, np.zeros(1, np.int64), np.full(1, grid * 4, np.int64))
-            N.check(lib.o3s_slab_range_sum(slab.data_ptr(), 0, L, lo.data_ptr(), cnt.data_ptr(), 1, y2.data_ptr(),
-                                           N.stream_of(Fm)), "gbt_leaf_pass y2")
-            y2 = y2[0]
-        return part.sum(0), y2
-    # torch reference: walk the tree, update, loss / residual, per-leaf y^2
+    f64 = [None if t is None else t.to(torch.float64).contiguous() for t in (wd, wv)]
+    wt32 = None if wt is None else wt.to(torch.float32).contiguous()
+    _check_target(target, n)
+    if not (yy.dtype == torch.float64 and Fm.dtype == torch.float64 and yy.is_contiguous() and Fm.is_contiguous()):
+        raise ValueError("yy / Fm must be contiguous fp64")
+    grid = int(max(1, min(N.num_cus(dev) * LEAF_BLOCKS_PER_CU, (n + 255) // 256)))
+    part = torch.empty((grid, 4), dtype=torch.float64, device=dev)
+    slab = torch.empty((grid * 4, L), dtype=torch.float32, device=dev) if need_y2 else None   # a row per wave
+    fb_d, val_d = N.upload_many(dev, fb, val)
+    st = N.stream_of(Fm)
+    N.check(N.kernels().o3s_gbt_leaf_pass(bins.data_ptr(), n, F, fb_d.data_ptr(), len(fb), val_d.data_ptr(), depth,
+                                          yy.data_ptr(), Fm.data_ptr(), N.ptr(wt32), N.ptr(f64[0]), N.ptr(f64[1]),
+                                          _GBT_LOSS[loss], int(first), N.ptr(target), part.data_ptr(), N.ptr(slab),
+                                          grid, st), "gbt_leaf_pass")
+    y2 = None
+    if need_y2:
+        y2 = torch.empty((1, L), dtype=torch.float64, device=dev)
+        lo, cnt = N.upload_many(dev, np.zeros(1, np.int64), np.full(1, grid * 4, np.int64))
+        _range_sums(slab, L, lo, cnt, y2, st)
+        y2 = y2[0]
+    return part.sum(0), y2
+
+
+def gbt_leaf_pass_torch(bins, feature, split_bin, value, scale, depth, loss, yy, Fm, wt, wd, wv, first, target,
+                        need_y2):
+    """Reference of ``gbt_leaf_pass``: walk the tree, update, loss / residual, per-leaf y^2."""
+    n = bins.shape[0]
+    dev = bins.device
+    fb, val = tree_node_arrays(feature, split_bin, value, scale)
+    L = 1 << depth
     fb_t = torch.from_numpy(fb.astype(np.int64)).to(dev)
     node = torch.ones(n, dtype=torch.int64, device=dev)
     for _ in range(depth):
@@ -354,7 +407,7 @@ def gbt_leaf_pass(bins: torch.Tensor, feature, split_bin, value, scale: float, d
         node = torch.where(inner, 2 * node + (b > sb).to(torch.int64), node)
     Fo = Fm.clone()
     Fm += torch.from_numpy(val).to(dev)[node]
-    out = gbt_grad_loss(loss, yy, Fm, wd, wv, target)
+    out = gbt_grad_loss_torch(loss, yy, Fm, wd, wv, target)
     y2 = None
     if need_y2:
         yo = yy.to(torch.float32) if first else gbt_residual(loss, yy.double(), Fo.double()).to(torch.float32)
@@ -374,7 +427,10 @@ def best_splits(H: torch.Tensor, nb: torch.Tensor, fmask, kind: str, min_inst: f
 
     ``fmask`` (numpy bool [k, F] or None): features each node may split on (forests);
     ``min_wfrac`` > 0: the minimum child weight is that fraction of the node's weight
-    (the root level), else ``min_w``; ``min_w_node`` (numpy [k]) overrides both per node."""
+    (the root level), else ``min_w``; ``min_w_node`` (numpy [k]) overrides both per node.
+    CPU: ``best_splits_torch``."""
+    if not H.is_cuda:
+        return best_splits_torch(H, nb, fmask, kind, min_inst, min_w, min_wfrac, min_w_node)
     k, F, B, S = H.shape
     dev = H.device
     Hc = H.to(torch.float64).contiguous()
@@ -384,10 +440,68 @@ def best_splits(H: torch.Tensor, nb: torch.Tensor, fmask, kind: str, min_inst: f
     mwn = None if min_w_node is None else N.upload(np.asarray(min_w_node, dtype=np.float64), dev)
     out = torch.empty(6 * k + k * V, dtype=torch.float64, device=dev)
     N.check(N.kernels().o3s_tree_split(Hc.data_ptr(), k, F, B, S, _KINDS[kind], nb32.data_ptr(), N.ptr(fm),
-                                       float(min_inst), float(min_w), float(min_wfrac),
-                                       N.ptr(mwn), out.data_ptr(),
+                                       float(min_inst), float(min_w), float(min_wfrac), N.ptr(mwn), out.data_ptr(),
                                        N.stream_of(Hc)), "tree_split")
     return out
+
+
+def _impurity(stats: torch.Tensor, kind: str) -> tuple[torch.Tensor, torch.Tensor]:
+    """stats [..., S] -> (impurity, weight)."""
+    if kind == "variance":
+        w = stats[..., 0]
+        mean = stats[..., 1] / w.clamp_min(1e-300)
+        imp = (stats[..., 2] / w.clamp_min(1e-300) - mean * mean).clamp_min(0.0)
+        return torch.where(w > 0, imp, torch.zeros_like(imp)), w
+    w = stats.sum(-1)
+    p = stats / w.clamp_min(1e-300)[..., None]
+    if kind == "gini":
+        imp = 1.0 - (p * p).sum(-1)
+    elif kind == "entropy":
+        imp = -(torch.where(p > 0, p * torch.log2(p.clamp_min(1e-300)), torch.zeros_like(p))).sum(-1)
+    else:
+        raise ValueError(kind)
+    return torch.where(w > 0, imp, torch.zeros_like(imp)), w
+
+
+def best_splits_torch(H, nb, fm, kind, min_inst, min_w, min_wfrac, min_w_node=None):
+    """Reference of ``tree_split_kernel``: the per-node decision bundle (fp64
+    [idx | gain | impurity | weight | wL | wR | values]) from histograms [k, F, B, S]."""
+    k = H.shape[0]
+    dev = H.device
+    cls, nb, bin_ids = kind != "variance", nb.to(dev), torch.arange(H.shape[2] - 1, device=dev)
+    tot = H[:, 0].sum(1)                                   # [k, S] node stats (feature 0 bins)
+    imp_p, w_p = _impurity(tot, kind)
+    vals = (tot / w_p.clamp_min(1e-300)[:, None]) if cls else (tot[:, 1] / w_p.clamp_min(1e-300))[:, None]
+    # split search: cumulative stats over bins (left = bins <= j)
+    cum = H.cumsum(2)                                      # [k, F, B, S]
+    left = cum[:, :, :-1]
+    right = tot[:, None, None, :] - left
+    W = w_p[:, None, None].clamp_min(1e-300)
+    if cls:
+        iL, wL = _impurity(left, kind)
+        iR, wR = _impurity(right, kind)
+        g = imp_p[:, None, None] - (wL / W) * iL - (wR / W) * iR
+    else:
+        # variance gain from (w, w*y) only: (SyL^2/wL + SyR^2/wR - Sy^2/W) / W
+        wL, wR = left[..., 0], right[..., 0]
+        sL, sR = left[..., 1], right[..., 1]
+        sP = tot[:, 1][:, None, None]
+        g = (sL * sL / wL.clamp_min(1e-300) + sR * sR / wR.clamp_min(1e-300) - sP * sP / W) / W
+    ok = (wL >= min_inst) & (wR >= min_inst)
+    if min_w_node is not None:
+        mw = torch.as_tensor(np.asarray(min_w_node, dtype=np.float64), device=dev)[:, None, None]
+    else:
+        mw = (min_wfrac * w_p)[:, None, None] if min_wfrac > 0.0 else torch.full_like(W, min_w)
+    ok &= (mw <= 0.0) | ((wL >= mw) & (wR >= mw))
+    ok &= bin_ids[None, None, :] < nb[None, :, None]
+    if fm is not None:
+        ok &= torch.from_numpy(fm).to(dev)[:, :, None]
+    g = torch.where(ok, g, torch.full_like(g, -math.inf))
+    best = g.reshape(k, -1).max(1)
+    # global child weights at the chosen split decide which child the next level scans
+    wl_best = wL.reshape(k, -1).gather(1, best.indices[:, None])[:, 0]
+    wr_best = wR.reshape(k, -1).gather(1, best.indices[:, None])[:, 0]
+    return torch.cat([best.indices.to(torch.float64), best.values, imp_p, w_p, wl_best, wr_best, vals.reshape(-1)])
 
 
 def partition_torch(bins, order, s_lo, s_hi, s_feat, s_bin, out=None, payload=(), payload_out=()):
@@ -452,23 +566,16 @@ def node_hist(bins: torch.Tensor, order: torch.Tensor, y: torch.Tensor, w: torch
     slab = torch.empty((plan.n_items, C), dtype=torch.float32, device=dev)
     yf = y.to(torch.float32).contiguous()
     wf = None if w is None else w.to(torch.float32).contiguous()
-    lib = N.kernels()
     st = N.stream_of(bins)
-    N.check(lib.o3s_tree_hist(bins.data_ptr(), bins.shape[0], F, B, S, int(cls), order.data_ptr(), yf.data_ptr(),
-                              N.ptr(wf), plan.it_lo.data_ptr(), plan.it_hi.data_ptr(), plan.n_items,
-                              slab.data_ptr(), int(bool(ypos)), st), "tree_hist")
+    N.check(N.kernels().o3s_tree_hist(bins.data_ptr(), bins.shape[0], F, B, S, int(cls), order.data_ptr(),
+                                      yf.data_ptr(), N.ptr(wf), plan.it_lo.data_ptr(), plan.it_hi.data_ptr(),
+                                      plan.n_items, slab.data_ptr(), int(bool(ypos)), st), "tree_hist")
     # ordered fp64 sums: runs of <= 64 item rows, then each segment's runs in order
     runs = torch.empty((plan.n_runs, C), dtype=torch.float64, device=dev)
-    for a in range(0, plan.n_runs, 65535):
-        b = min(a + 65535, plan.n_runs)
-        N.check(lib.o3s_slab_range_sum(slab.data_ptr(), 0, C, plan.r_lo[a:].data_ptr(), plan.r_cnt[a:].data_ptr(),
-                                       b - a, runs[a:].data_ptr(), st), "slab_range_sum")
+    _range_sums(slab, C, plan.r_lo, plan.r_cnt, runs, st)
     nseg = plan.nseg
     seg_sum = torch.empty((nseg, C), dtype=torch.float64, device=dev)
-    for a in range(0, nseg, 65535):
-        b = min(a + 65535, nseg)
-        N.check(lib.o3s_slab_range_sum(runs.data_ptr(), 1, C, plan.s_run0[a:].data_ptr(), plan.s_nrun[a:].data_ptr(),
-                                       b - a, seg_sum[a:].data_ptr(), st), "slab_range_sum")
+    _range_sums(runs, C, plan.s_run0, plan.s_nrun, seg_sum, st)
     if plan.identity and nseg == n_nodes:                 # the engine: segment i is node i
         return seg_sum.view(n_nodes, F, B, S)
     out = torch.zeros((n_nodes, C), dtype=torch.float64, device=dev)
@@ -482,30 +589,39 @@ def sibling_hists(Hs: torch.Tensor, parent: torch.Tensor, small_right, cls: bool
     the rounding residue of fractional weights cleaned (class counts / weights clamped
     at 0, REG w*y zeroed where w <= 0, the node's w*y^2 clamped at 0).
 
-    GPU: ``tree_sibling_kernel`` (one pass); CPU: torch."""
+    GPU: ``tree_sibling_kernel`` (one pass); CPU: ``sibling_torch`` + torch indexing."""
     P = Hs.shape[0]
     sr = np.asarray(small_right, dtype=np.uint8)
+    H = torch.empty((2 * P,) + tuple(Hs.shape[1:]), dtype=torch.float64, device=Hs.device)
     if Hs.is_cuda and P > 0:
         Hs_c, par = Hs.contiguous(), parent.contiguous()
-        H = torch.empty((2 * P,) + tuple(Hs.shape[1:]), dtype=torch.float64, device=Hs.device)
         srd = N.upload(sr, Hs.device)
         _, F, B, S = Hs.shape
         N.check(N.kernels().o3s_tree_sibling(Hs_c.data_ptr(), par.data_ptr(), srd.data_ptr(), P, F * B, S, int(cls),
                                              H.data_ptr(), N.stream_of(Hs)), "tree_sibling")
         return H
-    sib = parent - Hs
-    if cls:
-        sib.clamp_min_(0.0)
-    else:
-        y2 = sib[:, 0, 0, 2].clamp_min(0.0)
-        empty = sib[..., 0] <= 0.0
-        sib[..., :2] = torch.where(empty[..., None], torch.zeros_like(sib[..., :2]), sib[..., :2])
-        sib[:, 0, 0, 2] = y2
-    H = torch.empty((2 * P,) + tuple(Hs.shape[1:]), dtype=torch.float64, device=Hs.device)
     pick = torch.from_numpy(2 * np.arange(P) + sr.astype(np.int64)).to(Hs.device)
     H[pick] = Hs
-    H[pick ^ 1] = sib
+    H[pick ^ 1] = sibling_torch(parent, Hs, cls)
     return H
+
+
+def sibling_torch(parent: torch.Tensor, child: torch.Tensor, cls: bool) -> torch.Tensor:
+    """Histogram of the scanned child's sibling, parent - child ([P, F, B, S] fp64).
+
+    Both operands are exact ordered fp64 sums, but with fractional weights the
+    difference can still leave rounding residue in bins the sibling does not populate;
+    it is cleaned so such a bin reads as empty: weights / class counts are clamped at 0
+    and REG bins whose weight is not positive get zero w*y.  The REG node total of w*y^2
+    (feature 0, bin 0, stat 2) is only clamped at 0."""
+    sib = parent - child
+    if cls:
+        return sib.clamp_min_(0.0)
+    y2 = sib[:, 0, 0, 2].clamp_min(0.0)
+    empty = sib[..., 0] <= 0.0
+    sib[..., :2] = torch.where(empty[..., None], torch.zeros_like(sib[..., :2]), sib[..., :2])
+    sib[:, 0, 0, 2] = y2
+    return sib
 
 
 _RUN = 64      # slab rows per first-stage partial
@@ -521,17 +637,10 @@ class _HistPlan:
     instead of a dozen tiny device ops and syncs per tree level."""
 
     def __init__(self, seg_lo, seg_hi, seg_node, chunk: int, dev):
-        import numpy as np
         lo, hi, nd = _host(seg_lo), _host(seg_hi), _host(seg_node)
-        lens = np.maximum(hi - lo, 0)
-        n_it = (lens + chunk - 1) // chunk
-        first = np.cumsum(n_it) - n_it
+        seg_of, it_lo, it_hi, first, n_it = _plan_items(lo, hi, chunk)
         self.nseg = len(lo)
-        self.n_items = int(n_it.sum())
-        seg_of = np.repeat(np.arange(self.nseg), n_it)
-        k = np.arange(self.n_items) - first[seg_of]
-        it_lo = lo[seg_of] + k * chunk
-        it_hi = np.minimum(it_lo + chunk, hi[seg_of])
+        self.n_items = len(seg_of)
         n_run = (n_it + _RUN - 1) // _RUN
         run0 = np.cumsum(n_run) - n_run
         self.n_runs = int(n_run.sum())
@@ -541,11 +650,8 @@ class _HistPlan:
         r_cnt = np.minimum(_RUN, first[rseg] + n_it[rseg] - r_lo)
         parts = [it_lo, it_hi, r_lo, r_cnt, run0, n_run, nd]
         buf = N.upload(np.concatenate(parts).astype(np.int64), dev)
-        views, off = [], 0
-        for p in parts:
-            views.append(buf[off: off + len(p)])
-            off += len(p)
-        self.it_lo, self.it_hi, self.r_lo, self.r_cnt, self.s_run0, self.s_nrun, self.seg_node = views
+        self.it_lo, self.it_hi, self.r_lo, self.r_cnt, self.s_run0, self.s_nrun, self.seg_node = buf.split(
+            [len(p) for p in parts])
         self.identity = bool(np.array_equal(nd, np.arange(self.nseg)))
 
 

@@ -1,4 +1,6 @@
 """Trees: CPU path vs scikit-learn-level accuracy; GPU histogram kernel vs torch reference."""
+import functools
+
 import numpy as np
 import pandas as pd
 import pytest
@@ -169,7 +171,7 @@ def test_gpu_hist_subtraction_exact_with_heavy_fractional_weights(gpu, cls):
     """Sibling = parent - child equals a direct scan of the sibling when weights are
     fractional and a bin's weight is past 2^24 (fp64 ordered slab sums), and
     the histogram is bitwise reproducible across launches."""
-    from orange3_spark_amd.models.trees import _sibling
+    from orange3_spark_amd.ops.trees import sibling_torch
     from orange3_spark_amd.ops import trees as T
     g = torch.Generator().manual_seed(11)
     n, F, B = 400_003, 8, 16
@@ -191,7 +193,7 @@ def test_gpu_hist_subtraction_exact_with_heavy_fractional_weights(gpu, cls):
     child = T.node_hist(bins, order, y, w, torch.tensor([0], device=gpu), torch.tensor([split], device=gpu),
                         nd, 1, B, S, cls)
     direct = T.node_hist(bins, order, y, w, torch.tensor([split], device=gpu), hi_p, nd, 1, B, S, cls)
-    sib = _sibling(parent, child, cls)
+    sib = sibling_torch(parent, child, cls)
     ref = T.hist_torch(bins, order, y, w, torch.tensor([split], device=gpu), hi_p, nd, 1, B, S, cls)
     torch.testing.assert_close(direct, ref, rtol=1e-6, atol=1.0)   # fp32 per-item partials, fp64 sums
     torch.testing.assert_close(sib, ref, rtol=1e-6, atol=1.0)
@@ -322,7 +324,7 @@ def test_partition_payload_torch():
 @pytest.mark.parametrize("kind,S", [("variance", 3), ("gini", 2), ("entropy", 5), ("gini", 12)])
 def test_gpu_split_kernel_matches_torch(gpu, kind, S):
     """tree_split_kernel (one fused launch per level) == the torch split search."""
-    from orange3_spark_amd.models.trees import _split_bundle_torch
+    from orange3_spark_amd.ops.trees import best_splits_torch
     from orange3_spark_amd.ops import trees as T
     g = torch.Generator().manual_seed(S)
     k, F, B = 37, 20, 16
@@ -337,10 +339,9 @@ def test_gpu_split_kernel_matches_torch(gpu, kind, S):
     H[3] = 0.0                                                        # an empty node
     nb = torch.randint(1, B, (F,), generator=g)
     fm = (torch.rand((k, F), generator=g) < 0.5).numpy()
-    bin_ids = torch.arange(B - 1)
     for fmask, mi, mw, mwf in ((None, 1.0, 0.0, 0.0), (fm, 30.0, 0.0, 0.0), (fm, 1.0, 0.0, 0.2), (None, 1.0, 90.0, 0.0)):
-        ref = _split_bundle_torch(H, kind, kind != "variance", nb, bin_ids, fmask, mi, mw, mwf)
-        got = T.best_splits(H.to(gpu), nb.to(gpu), fmask, kind, mi, mw, mwf).cpu()
+        ref = best_splits_torch(H, nb, fmask, kind, mi, mw, mwf)
+        got =T.best_splits(H.to(gpu), nb.to(gpu), fmask, kind, mi, mw, mwf).cpu()
         fin = torch.isfinite(ref[k:2 * k])
         assert torch.equal(fin, torch.isfinite(got[k:2 * k]))
         assert torch.equal(ref[:k][fin], got[:k][fin])                # same split (no exact ties here)
@@ -348,6 +349,95 @@ def test_gpu_split_kernel_matches_torch(gpu, kind, S):
         torch.testing.assert_close(got[2 * k:4 * k], ref[2 * k:4 * k], rtol=1e-12, atol=1e-12)
         torch.testing.assert_close(got[4 * k:6 * k][fin.repeat(2)], ref[4 * k:6 * k][fin.repeat(2)])
         torch.testing.assert_close(got[6 * k:], ref[6 * k:], rtol=1e-12, atol=1e-12)
+
+
+def test_best_splits_on_cpu_is_the_torch_reference():
+    from orange3_spark_amd.ops import trees as T
+    g = torch.Generator().manual_seed(2)
+    H = torch.rand((5, 4, 8, 3), generator=g, dtype=torch.float64) * 9
+    nb = torch.tensor([7, 3, 5, 1])
+    fm = (torch.rand((5, 4), generator=g) < 0.6).numpy()
+    for kind in ("variance", "gini"):
+        args = (H, nb, fm, kind, 1.0, 0.0, 0.1)
+        assert torch.equal(T.best_splits(*args), T.best_splits_torch(*args))
+
+
+# the work-item planner's edge cases at chunk 4096: an empty segment, a one-row segment, a
+# segment of exactly one chunk, and chunk-row segments followed by a remainder
+_CHUNK = 4096
+_N = 3 * _CHUNK + 5
+_CUTS = np.array([0, 0, 1, 4097, 8193, _N], dtype=np.int64)
+
+
+@functools.lru_cache(None)
+def _last_level_case():
+    """Inputs shared by the final_level / leaf_apply kernel checks (read-only: tests clone ``acc``)."""
+    g = torch.Generator().manual_seed(6)
+    F = 13
+    d = {"bins": torch.randint(0, 32, (_N, F), generator=g, dtype=torch.uint8),
+         "order": torch.randperm(_N, generator=g).to(torch.int32),
+         "lo": _CUTS[:-1].copy(), "hi": _CUTS[1:].copy(),
+         "feat": torch.randint(0, F, (5,), generator=g).numpy(), "bin": torch.randint(0, 31, (5,), generator=g).numpy(),
+         "vl": torch.randn(5, generator=g, dtype=torch.float64).numpy(),
+         "vr": torch.randn(5, generator=g, dtype=torch.float64).numpy(),
+         "y": torch.randn(_N, generator=g), "w": torch.rand(_N, generator=g),
+         "acc": torch.randn(_N, generator=g, dtype=torch.float64)}
+    return d
+
+
+def test_plan_items_bounds_and_sum_order():
+    """The planner against a straight-line recomputation: every segment is cut, in order,
+    into items of <= chunk rows, and segment s sums exactly its own items
+    [first[s], first[s] + n_it[s]) in item order (the fixed fp64 summation order)."""
+    from orange3_spark_amd.ops import trees as T
+    lo, hi = _CUTS[:-1], _CUTS[1:]
+    seg_of, it_lo, it_hi, first, n_it = T._plan_items(lo, hi, _CHUNK)
+    items = [(s, a, min(a + _CHUNK, int(hi[s]))) for s in range(len(lo)) for a in range(int(lo[s]), int(hi[s]), _CHUNK)]
+    assert [tuple(map(int, t)) for t in zip(seg_of, it_lo, it_hi)] == items
+    assert n_it.tolist() == [0, 1, 1, 1, 2]
+    for s in range(len(lo)):
+        assert list(range(int(first[s]), int(first[s] + n_it[s]))) == [i for i, t in enumerate(items) if t[0] == s]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("feature_major", [False, True])
+@pytest.mark.parametrize("weighted", [False, True])
+def test_gpu_final_level_matches_torch(gpu, feature_major, weighted):
+    """tree_final_level_kernel == final_level_torch: ``acc`` exactly (one fp64 add per row
+    of a value both sides compute identically); the children's w*y^2 sums to the error of
+    fp32 per-item partials.  Every term w*y^2 is >= 0, so a partial over m <= 4096 rows
+    (two roundings per term, m - 1 fp32 additions in any order: k = m + 1 roundings of
+    u = 2^-24 on any path) is within k*u / (1 - k*u) of its exact value, relatively, and so
+    is the sum of the partials; 2^-40 covers the fp64 sums on both sides."""
+    from orange3_spark_amd.ops import trees as T
+    c = _last_level_case()
+    w = c["w"] if weighted else None
+    acc_ref = c["acc"].clone()
+    ref = T.final_level_torch(c["bins"], c["order"], c["lo"], c["hi"], c["feat"], c["bin"], c["vl"], c["vr"], c["y"], w,
+                              acc_ref, True)
+    bins = c["bins"].to(gpu)
+    acc = c["acc"].to(gpu)
+    got = T.final_level(bins, c["order"].to(gpu), c["lo"], c["hi"], c["feat"], c["bin"], c["vl"], c["vr"],
+                        c["y"].to(gpu), None if w is None else w.to(gpu), acc, True,
+                        bins_t=T.feature_major(bins) if feature_major else None, chunk=_CHUNK)
+    assert torch.equal(acc.cpu(), acc_ref) and not torch.equal(acc_ref, c["acc"])
+    assert got.dtype == torch.float64 and float(ref[0].abs().sum()) == 0.0 and bool((ref[1:].sum(1) > 0).all())
+    ku = (_CHUNK + 1) * 2.0 ** -24
+    print("final_level y2 max relative error:", float(((got.cpu() - ref).abs() / ref.clamp_min(1e-300)).max()),
+          "bound:", ku / (1 - ku) + 2.0 ** -40)
+    torch.testing.assert_close(got.cpu(), ref, rtol=ku / (1 - ku) + 2.0 ** -40, atol=0.0)
+
+
+@pytest.mark.gpu
+def test_gpu_leaf_apply_matches_torch(gpu):
+    """tree_leaf_apply_kernel == leaf_apply_torch, exactly (one fp64 add per row)."""
+    from orange3_spark_amd.ops import trees as T
+    c = _last_level_case()
+    acc_ref = c["acc"].clone()
+    T.leaf_apply_torch(c["order"], c["lo"], c["hi"], c["vl"], acc_ref)
+    acc = c["acc"].to(gpu)
+    T.leaf_apply(c["order"].to(gpu), c["lo"], c["hi"], c["vl"], acc, chunk=_CHUNK)
+    assert torch.equal(acc.cpu(), acc_ref) and not torch.equal(acc_ref, c["acc"])
 
 
 @pytest.mark.gpu
@@ -433,7 +523,7 @@ def test_gpu_forest_weights_kernel_matches_sampling(gpu, bootstrap, rate, monkey
     n = 100_003
     rows = torch.arange(5_000, 5_000 + n, dtype=torch.int64)
     w = torch.rand(n, generator=torch.Generator().manual_seed(1))
-    ref = [TR.subsample_weights(None, rows, rate, 11 * 7919 + t, bootstrap) * w for t in range(3)]
+    ref = [TR.subsample_weights(rows, rate, 11 * 7919 + t, bootstrap) * w for t in range(3)]
     seen = {}
 
     class _Stop(Exception):

@@ -24,6 +24,7 @@ def main():
     import numpy as np
     import torch
     from orange3_spark_amd.models import trees as TR
+    from orange3_spark_amd.ops import trees as T
     n, F = a.rows, a.features
     dev = torch.device("cuda")
     X = torch.empty((n, F), dtype=torch.bfloat16, device=dev)
@@ -42,14 +43,14 @@ def main():
     for lay in ("1", "0"):
         os.environ["O3S_BIN_EYT"] = lay
         for name, ot in (("with_feature_major", out_t), ("row_major_only", None)):
-            TR._bin_block_kernel(X, tht, Tp, out, ot, n)
+            T.bin_block(X, tht, Tp, out, ot, n)
             torch.cuda.synchronize()
             if ot is not None:
                 sig[lay] = (int(out[:: 997].sum()), int(out_t[:, :: 997].sum()))
             ts = []
             for _ in range(a.reps):
                 t = time.perf_counter()
-                TR._bin_block_kernel(X, tht, Tp, out, ot, n)
+                T.bin_block(X, tht, Tp, out, ot, n)
                 torch.cuda.synchronize()
                 ts.append(time.perf_counter() - t)
             ms = 1e3 * min(ts)
