@@ -1224,11 +1224,16 @@ O3S_API int o3s_gbt_leaf_pass(const uint8_t* bins, int64_t n, int F, const int32
   if (F <= 0 || F > 0xffff || nodes <= 1 || D < 0 || D > 10 || loss < 0 || loss > 2 || grid <= 0) return -1;
   const int L = 1 << D;
   const bool y2 = y2slab != nullptr;
-  const bool stage = (F % 16) == 0 && F <= 256 && ((uintptr_t)bins & 15) == 0;
-  const int Fs = stage ? ((F / 4) % 2 == 0 ? F + 4 : F) : 0;
-  const size_t lds = 4 * (size_t)((nodes + 3) & ~3) + (y2 ? 4 * (size_t)kLeafWaves * L : 0) +
-                     (size_t)kLeafWaves * 64 * Fs;
-  if (lds > 64 * 1024) return -2;
+  // the tree and the per-wave leaf sums (<= 8 KB + 16 KB at 2^11 nodes, D = 10) always fit;
+  // the row stage is taken only where it fits beside them in 64 KB (F = 256, or F >= 192
+  // at the deepest trees, does not): those shapes read their split bytes from global memory
+  const size_t lds0 = 4 * (size_t)((nodes + 3) & ~3) + (y2 ? 4 * (size_t)kLeafWaves * L : 0);
+  const int Fs1 = (F / 4) % 2 == 0 ? F + 4 : F;
+  const bool stage = (F % 16) == 0 && F <= 256 && ((uintptr_t)bins & 15) == 0 &&
+                     lds0 + (size_t)kLeafWaves * 64 * Fs1 <= 64 * 1024;
+  const int Fs = stage ? Fs1 : 0;
+  const size_t lds = lds0 + (size_t)kLeafWaves * 64 * Fs;
+  if (lds > 64 * 1024) return -2;                        // nodes beyond a depth-10 heap
 #define O3S_LP(S, Y)                                                                                       \
   hipLaunchKernelGGL((gbt_leaf_pass_kernel<S, Y>), dim3(grid), dim3(kLeafThreads), lds, st, bins, n, F, Fs,   \
                      node_fb, nodes, node_val, D, yy, Fm, wt, wd, wv, loss, first, target, partial, y2slab, L)

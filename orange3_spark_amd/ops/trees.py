@@ -359,6 +359,8 @@ def gbt_leaf_pass(bins: torch.Tensor, feature, split_bin, value, scale: float, d
     the pre-update Fm) -- the last level's children impurities.  CPU: ``gbt_leaf_pass_torch``."""
     n, F = bins.shape
     dev = bins.device
+    if not bins.is_contiguous():                     # the kernel reads row i at bins + i * F
+        raise ValueError("bins must be a contiguous [n, F] matrix")
     if not (bins.is_cuda and n > 0):
         return gbt_leaf_pass_torch(bins, feature, split_bin, value, scale, depth, loss, yy, Fm, wt, wd, wv, first,
                                    target, need_y2)

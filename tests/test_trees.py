@@ -587,26 +587,39 @@ def test_gpu_final_level_from_parent_matches_full_level():
     _final_level_parity(Session(SessionConf().set("o3s.device", "cuda")))
 
 
-def _gbt_fused_parity(session):
+def _gbt_fused_parity(session, F=7):
     """fit_gbt's fused row-order epilogue (ops/trees.gbt_leaf_pass: every leaf applied,
     the loss, the next residuals and the last level's w*y^2 in one pass) == the reference
     path (per-level leaf_apply + last-level routing + gbt_grad_loss): trees, losses,
     impurities, predictions -- logistic with validation + subsampling, squared and
-    absolute losses with weights."""
+    absolute losses with weights.
+
+    ``F`` = 256: feature sets too wide for the leaf pass to stage its rows in LDS (256
+    features at any depth, the first 192 of them at depth 10)."""
     from orange3_spark_amd.models import trees as TR
     rng = np.random.default_rng(21)
-    n = 6000
-    X = rng.uniform(-1, 1, size=(n, 7))
+    n = 6000 if F == 7 else 1500
+    X = rng.uniform(-1, 1, size=(n, F))
     yc = ((X[:, 0] > 0.1) ^ (X[:, 2] > -0.3)).astype(float)
     yr = np.sin(3 * X[:, 0]) + X[:, 1] * X[:, 3] + 0.1 * rng.normal(size=n)
     w = rng.uniform(0.5, 2.0, size=n)
     val = rng.random(n) < 0.2
-    dfc = session.createDataFrame(pd.DataFrame({"features": list(X), "label": yc, "w": w, "v": val}))
-    dfr = session.createDataFrame(pd.DataFrame({"features": list(X), "label": yr, "w": w}))
-    makers = [(dfc, lambda: GBTClassifier(maxDepth=5, maxIter=6, subsamplingRate=0.8, seed=3,
-                                          validationIndicatorCol="v", validationTol=0.0)),
-              (dfr, lambda: GBTRegressor(maxDepth=4, maxIter=5, weightCol="w", lossType="squared")),
-              (dfr, lambda: GBTRegressor(maxDepth=6, maxIter=4, weightCol="w", lossType="absolute"))]
+    if F == 7:
+        dfc = session.createDataFrame(pd.DataFrame({"features": list(X), "label": yc, "w": w, "v": val}))
+        dfr = session.createDataFrame(pd.DataFrame({"features": list(X), "label": yr, "w": w}))
+        makers = [(dfc, lambda: GBTClassifier(maxDepth=5, maxIter=6, subsamplingRate=0.8, seed=3,
+                                              validationIndicatorCol="v", validationTol=0.0)),
+                  (dfr, lambda: GBTRegressor(maxDepth=4, maxIter=5, weightCol="w", lossType="squared")),
+                  (dfr, lambda: GBTRegressor(maxDepth=6, maxIter=4, weightCol="w", lossType="absolute"))]
+    else:
+        dfc = session.createDataFrame(pd.DataFrame({"features": list(X[:, :192]), "label": yc}))
+        dfr = session.createDataFrame(pd.DataFrame({"features": list(X), "label": yr}))
+        dfr192 = session.createDataFrame(pd.DataFrame({"features": list(X[:, :192]), "label": yr}))
+        # (the classifier's trees end above depth 10 on these rows, so its leaf pass carries no
+        # w*y^2 sums; the depth-10 regressor's does: tree + leaf sums + a 192-byte row stage)
+        makers = [(dfr, lambda: GBTRegressor(maxDepth=3, maxIter=3)),
+                  (dfc, lambda: GBTClassifier(maxDepth=10, maxIter=2)),
+                  (dfr192, lambda: GBTRegressor(maxDepth=10, maxIter=2))]
     for df, mk in makers:
         outs = []
         for flag in (True, False):
@@ -636,6 +649,15 @@ def test_gbt_fused_epilogue_matches_reference(cpu):
 @pytest.mark.gpu
 def test_gpu_gbt_fused_epilogue_matches_reference():
     _gbt_fused_parity(Session(SessionConf().set("o3s.device", "cuda")))
+
+
+def test_gbt_fused_epilogue_matches_reference_on_wide_features(cpu):
+    _gbt_fused_parity(cpu, F=256)
+
+
+@pytest.mark.gpu
+def test_gpu_gbt_fused_epilogue_matches_reference_on_wide_features():
+    _gbt_fused_parity(Session(SessionConf().set("o3s.device", "cuda")), F=256)
 
 
 @pytest.mark.gpu
