@@ -24,7 +24,14 @@ key                            meaning here
                                ``respawn`` (true)
 ``o3s.device``                 ``auto`` | ``cuda`` | ``cpu``
 ``o3s.vector.dtype``           feature-matrix storage: ``auto`` (bf16 on GPU, f64 on
-                               CPU) | ``bfloat16`` | ``float32`` | ``float64``
+                               CPU) | ``bfloat16`` | ``float32`` | ``float64``.  On a
+                               GPU, ``bfloat16`` and ``float32`` rows are zero padded to
+                               a multiple of 8 columns and are what the fused assembler
+                               and the GLM kernels (binary LogisticRegression, LinearSVC,
+                               LinearRegression l-bfgs / sgd, their predictions) stream;
+                               ``float32`` keeps 24 significant bits of the table
+                               (bf16: 8) at twice the bytes per pass.  Multinomial
+                               fits, KMeans and tree binning compute from either.
 ``o3s.memory.fraction``        share of free HBM the DataFrame cache may pin (0.85)
 ``spark.sql.warehouse.dir``    catalog ("Hive") root directory
 ``o3s.seed``                   default RNG seed (sample/randomSplit/estimators)

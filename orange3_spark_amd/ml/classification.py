@@ -200,9 +200,10 @@ class LogisticRegressionModel(U.ProbabilisticClassifierMixin, Model, _LogisticRe
         if isinstance(c, SpilledVectorColumn) and c.data.is_cuda and c.data.dtype == torch.bfloat16 \
                 and not self._multinomial:
             return c                 # resident + host-streamed rows -> margin kernel per chunk
-        if isinstance(c, C.VectorColumn) and c.data.is_cuda and c.data.dtype == torch.bfloat16 \
+        if isinstance(c, C.VectorColumn) and c.data.is_cuda \
+                and (c.data.dtype == torch.bfloat16 or G.f32_rows(c.data)) \
                 and not self._multinomial and not isinstance(c, (LineageVectorColumn, SpilledVectorColumn)):
-            return c.data            # padded bf16 -> margin kernel
+            return c.data            # padded bf16 / fp32 -> margin kernel
         if isinstance(c, C.SparseVectorColumn) and not self._multinomial:
             return U.linear_features(df, name)     # CSR rows -> sparse margin kernel
         return U.dense_features(df, name)
@@ -214,7 +215,7 @@ class LogisticRegressionModel(U.ProbabilisticClassifierMixin, Model, _LogisticRe
             m = map_rows(X, lambda Xc: G.glm_margin(Xc, w, float(self._b[0])).double())
             return torch.stack([-m, m], dim=1)
         if not self._multinomial:
-            if isinstance(X, torch.Tensor) and X.is_cuda and X.dtype == torch.bfloat16:
+            if isinstance(X, torch.Tensor) and X.is_cuda and (X.dtype == torch.bfloat16 or G.f32_rows(X)):
                 m = G.glm_margin(X, torch.from_numpy(self._B[0]).float().to(X.device), float(self._b[0])).double()
             else:
                 m = U.linear_margin(X, self._B[0], float(self._b[0]))
@@ -338,13 +339,13 @@ class LinearSVCModel(U.ProbabilisticClassifierMixin, Model, _LinearSVCParams, ML
         return int(self._w.shape[0])
 
     def _features_for_predict(self, df, name):
-        return U.linear_features(df, name)        # sparse rows stay CSR
+        return U.margin_features(df, name)        # sparse rows stay CSR, padded fp32 rows as stored
 
     def _raw(self, X):
         if isinstance(X, torch.Tensor) and X.is_cuda and X.dtype == torch.bfloat16:
             m = G.glm_margin(X, torch.from_numpy(self._w).float().to(X.device), self._b).double()
         else:
-            m = U.linear_margin(X, self._w, self._b)
+            m = U.glm_margin(X, self._w, self._b)
         return torch.stack([-m, m], dim=1)
 
     def _raw2prob(self, raw):
@@ -354,7 +355,11 @@ class LinearSVCModel(U.ProbabilisticClassifierMixin, Model, _LinearSVCParams, ML
         return (raw[:, 1] > self.getOrDefault(self.threshold)).to(torch.float64)
 
     def _transform(self, df):
-        X = U.dense_features(df, self.getOrDefault(self.featuresCol))
+        c = U.features_column(df, self.getOrDefault(self.featuresCol))
+        if type(c) is C.VectorColumn and G.f32_rows(c.data):
+            X = c.data               # padded fp32 rows -> margin kernel
+        else:
+            X = U.dense_features(df, self.getOrDefault(self.featuresCol))
         raw = self._raw(X)
         out = df
         if self.getOrDefault(self.rawPredictionCol):

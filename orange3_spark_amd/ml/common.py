@@ -40,6 +40,28 @@ def linear_features(df, name: str):
     return dense_features(df, name)
 
 
+def margin_features(df, name: str):
+    """:func:`linear_features`, except that a GPU fp32 vector column stored in the GLM
+    kernels' padded row layout is handed over as stored (ops.glm.glm_margin streams it; no
+    fp64 copy of the rows)."""
+    from ..frame.spill import SpilledVectorColumn
+    from ..ops import glm as G
+    c = features_column(df, name)
+    if isinstance(c, C.VectorColumn) and not isinstance(c, (LineageVectorColumn, SpilledVectorColumn)) \
+            and G.f32_rows(c.data):
+        return c.data
+    return linear_features(df, name)
+
+
+def glm_margin(X, w: np.ndarray, b: float) -> torch.Tensor:
+    """Margins of a fitted GLM as fp64: fp32 kernel rows (:func:`margin_features`) go through
+    the margin kernel, every other operand through :func:`linear_margin`."""
+    from ..ops import glm as G
+    if isinstance(X, torch.Tensor) and G.f32_rows(X) and X.shape[1] >= len(w):
+        return G.glm_margin(X, torch.from_numpy(np.asarray(w, dtype=np.float32)).to(X.device), float(b)).double()
+    return linear_margin(X, w, b)
+
+
 def linear_margin(X, w: np.ndarray, b: float) -> torch.Tensor:
     """fp64 margins X.w + b for a dense tensor or SparseRows operand."""
     from ..ops.sparse import SparseRows

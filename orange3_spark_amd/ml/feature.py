@@ -35,12 +35,13 @@ from .util import MLReadable, MLWritable, apply_metadata, prim_list, read_data, 
 
 # ----------------------------------------------------------------------------- helpers
 def to_vector_column(session, mat: torch.Tensor, size: int | None = None) -> C.VectorColumn:
-    """Store a dense [n, d] matrix in the session's feature dtype (bf16 padded on GPU)."""
+    """Store a dense [n, d] matrix in the session's feature dtype (bf16, and fp32 on the GPU,
+    zero padded to the kernels' row stride)."""
     dt = session.vector_dtype()
     n, d = mat.shape
-    if dt == torch.bfloat16:
+    if dt == torch.bfloat16 or (dt == torch.float32 and mat.is_cuda):
         ld = G.padded_width(d)
-        out = torch.zeros((n, ld), dtype=torch.bfloat16, device=mat.device)
+        out = torch.zeros((n, ld), dtype=dt, device=mat.device)
         out[:, :d] = mat
         return C.VectorColumn(out, d if size is None else size)
     return C.VectorColumn(mat.to(dt).contiguous(), d if size is None else size)
@@ -212,13 +213,13 @@ class VectorAssembler(Transformer, HasInputCols, HasOutputCol, HasHandleInvalid,
         return df.withColumnData(self.getOrDefault(self.outputCol), out)
 
     def _transform_fused(self, df, cols, n):
-        """GPU, bf16 feature storage: ONE gather kernel (ops/assemble.py) reads every input
-        column once (any numeric dtype, null masks, vector columns) and writes the padded
-        bf16 matrix once, flagging invalid rows in the same pass; None -> torch path."""
+        """GPU, bf16 or fp32 feature storage: ONE gather kernel (ops/assemble.py) reads every
+        input column once (any numeric dtype, null masks, vector columns) and writes the padded
+        matrix once, flagging invalid rows in the same pass; None -> torch path."""
         from ..ops import assemble as A
         from ..synthetic import LineageVectorColumn
-        if df.device.type != "cuda" or df.session.vector_dtype() != torch.bfloat16 or not cols or n == 0 \
-                or len(cols) > A.MAX_SOURCES:
+        vdt = df.session.vector_dtype()
+        if df.device.type != "cuda" or vdt not in A.OUT_DTYPES or not cols or n == 0 or len(cols) > A.MAX_SOURCES:
             return None
         srcs = []
         for c in cols:
@@ -230,7 +231,7 @@ class VectorAssembler(Transformer, HasInputCols, HasOutputCol, HasHandleInvalid,
                 srcs.append((col.data, None, int(col.size)))
             else:
                 return None
-        out, bad, nbad, D = A.assemble_bf16(srcs, n, df.device)
+        out, bad, nbad, D = A.assemble(srcs, n, df.device, vdt)
         nb = int(nbad.item())
         if nb:
             hi = self.getOrDefault(self.handleInvalid)

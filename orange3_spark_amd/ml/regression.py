@@ -156,10 +156,10 @@ class LinearRegressionModel(U.PredictionModelMixin, Model, _LinearRegressionPara
         return 1.0
 
     def _features_for_predict(self, df, name):
-        return U.linear_features(df, name)        # sparse rows stay CSR
+        return U.margin_features(df, name)        # sparse rows stay CSR, padded fp32 rows as stored
 
     def _predict_tensor(self, X):
-        return U.linear_margin(X, self._w, self._b)
+        return U.glm_margin(X, self._w, self._b)
 
     def evaluate(self, df):
         """Evaluate on ``df``: a LinearRegressionSummary (metrics computed lazily)."""

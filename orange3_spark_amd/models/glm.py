@@ -61,7 +61,10 @@ class GlmData:
         self.d = int(feat.size)
         self.X = X
         self.device = X.device if X.numel() or X.is_cuda else y.device
-        self.kernel = X.is_cuda and X.dtype == torch.bfloat16 and X.is_contiguous()
+        # the HIP passes: bf16 rows, or resident fp32 rows padded to the kernels' row stride
+        # (spilled / host-streamed fp32 rows keep the chunked torch pass)
+        self.kernel = X.is_cuda and X.is_contiguous() and (
+            X.dtype == torch.bfloat16 or (G.f32_rows(X) and not isinstance(feat, SpilledVectorColumn)))
         self.ld = int(X.shape[1])
         self.y = y.to(self.device, torch.float32).contiguous() if self.kernel else y.to(self.device)
         self.sw = None if sw is None else (sw.to(self.device, torch.float32).contiguous() if self.kernel else sw.to(self.device))
@@ -575,7 +578,11 @@ def fit_glm(data: GlmData, loss: str, reg=0.0, alpha=0.0, fit_intercept=True, st
         r = optim.owlqn(obj.smooth, x0, l1, max_iter=left, tol=tol, callback=save)
         res = GlmResult(r.x, 0.0, r.history, done + r.iterations, r.converged)
     else:
-        r = optim.lbfgs(obj.smooth, x0, max_iter=left, tol=tol, callback=save)
+        # fp32 rows: the caller asked for more than bf16 precision, and near the optimum one
+        # iteration's decrease sinks below the fp32 rounding of the kernel's per-row losses;
+        # without a noise floor the line search then fails tens of iterations early
+        f32 = isinstance(data, GlmData) and data.kernel and data.X.dtype == torch.float32
+        r = optim.lbfgs(obj.smooth, x0, max_iter=left, tol=tol, callback=save, f_noise=2.0 ** -24 if f32 else 0.0)
         res = GlmResult(r.x, 0.0, r.history, done + r.iterations, r.converged)
     if ckpt is not None:
         ckpt.clear()                     # finished: a later fit must not resume from this run
@@ -768,7 +775,7 @@ class DeviceSGD:
         d = self.data
         if d.spill is not None:               # host-streamed rows: copies + events stay eager
             return
-        if mode != "force" and d.n_local * d.ld * 2 > self.GRAPH_MAX_BYTES:
+        if mode != "force" and d.n_local * d.ld * d.X.element_size() > self.GRAPH_MAX_BYTES:
             return
         if d.comm.world_size > 1 and mode != "all":
             # multi-rank: pass and update graphs around an eager RCCL all-reduce are opt-in

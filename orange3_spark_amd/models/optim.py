@@ -28,9 +28,12 @@ class OptimResult:
     reason: str = ""
 
 
-def _strong_wolfe(fg: Fn, x, f0, g0, d, t0=1.0, c1=1e-4, c2=0.9, max_evals=20):
-    """Strong-Wolfe line search (bracketing + cubic/bisection zoom)."""
+def _strong_wolfe(fg: Fn, x, f0, g0, d, t0=1.0, c1=1e-4, c2=0.9, max_evals=20, f_noise=0.0):
+    """Strong-Wolfe line search (bracketing + cubic/bisection zoom).  ``f_noise``: relative
+    rounding noise of the function values; an increase below ``f_noise * |f0|`` does not
+    count as one (the gradient still has to meet the curvature condition)."""
     dg0 = float(g0 @ d)
+    nf = f_noise * abs(f0)
     if dg0 >= 0:
         return None
     t_prev, f_prev, dg_prev = 0.0, f0, dg0
@@ -44,7 +47,7 @@ def _strong_wolfe(fg: Fn, x, f0, g0, d, t0=1.0, c1=1e-4, c2=0.9, max_evals=20):
         dg = float(g @ d)
         if np.isfinite(f) and f < best[1]:
             best = (t, f, g)
-        if not np.isfinite(f) or f > f0 + c1 * t * dg0 or (evals > 1 and f >= f_prev):
+        if not np.isfinite(f) or f > f0 + c1 * t * dg0 + nf or (evals > 1 and f >= f_prev + nf):
             lo, hi = (t_prev, f_prev, dg_prev), (t, f, dg)
             break
         if abs(dg) <= -c2 * dg0:
@@ -68,7 +71,7 @@ def _strong_wolfe(fg: Fn, x, f0, g0, d, t0=1.0, c1=1e-4, c2=0.9, max_evals=20):
         dg = float(g @ d)
         if np.isfinite(f) and f < best[1]:
             best = (t, f, g)
-        if not np.isfinite(f) or f > f0 + c1 * t * dg0 or f >= fa:
+        if not np.isfinite(f) or f > f0 + c1 * t * dg0 + nf or f >= fa + nf:
             hi = (t, f, dg)
         else:
             if abs(dg) <= -c2 * dg0:
@@ -94,7 +97,9 @@ def _cubic_min(a, fa, da, b, fb, db):
 
 
 def lbfgs(fg: Fn, x0: np.ndarray, max_iter: int = 100, tol: float = 1e-6, m: int = 10,
-          callback=None) -> OptimResult:
+          callback=None, f_noise: float = 0.0) -> OptimResult:
+    """``f_noise``: relative rounding noise of ``fg``'s function values (0: exact), see
+    :func:`_strong_wolfe`."""
     x = np.array(x0, dtype=np.float64)
     f, g = fg(x)
     hist = [f]
@@ -118,7 +123,7 @@ def lbfgs(fg: Fn, x0: np.ndarray, max_iter: int = 100, tol: float = 1e-6, m: int
             q += (a - b) * s
         d = -q
         t0 = 1.0 if S else min(1.0, 1.0 / max(np.linalg.norm(g), 1e-12))
-        ls = _strong_wolfe(fg, x, f, g, d, t0)
+        ls = _strong_wolfe(fg, x, f, g, d, t0, f_noise=f_noise)
         if ls is None:
             res.reason = "line search failed"
             break

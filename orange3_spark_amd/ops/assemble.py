@@ -1,6 +1,6 @@
 """VectorAssembler gather kernel (csrc/assemble.hip): numeric / vector columns of any
-dtype, with null masks, -> one padded bf16 feature matrix in a single pass, plus per-row
-invalid flags and their count (handleInvalid).  CPU tensors are handled by the caller's
+dtype, with null masks, -> one padded bf16 or fp32 feature matrix in a single pass, plus
+per-row invalid flags and their count (handleInvalid).  CPU tensors are handled by the caller's
 torch path (ml/feature.py)."""
 from __future__ import annotations
 
@@ -22,7 +22,6 @@ def supported(t: torch.Tensor) -> bool:
 
 
 
-
 def _cols_ok(sources) -> bool:
     """Fast-path eligibility (assemble_cols_kernel): plain contiguous [n] float / double
     columns, all of one dtype."""
@@ -31,11 +30,22 @@ def _cols_ok(sources) -> bool:
         t.dtype == dt and t.dim() == 1 and t.stride(0) == 1 and int(w) == 1 for t, _, w in sources)
 
 
+OUT_DTYPES = (torch.bfloat16, torch.float32)
+
+
 def assemble_bf16(sources, n: int, device, path: str = "auto"):
+    """:func:`assemble` into bf16 rows."""
+    return assemble(sources, n, device, torch.bfloat16, path)
+
+
+def assemble(sources, n: int, device, dtype=torch.bfloat16, path: str = "auto"):
     """``sources``: list of (tensor [n] or [n, >= width] row-major, valid bool [n] or None,
-    width).  Returns (bf16 [n, ld] zero padded, uint8 invalid flags [n], invalid count).
-    ``path``: "auto" (column-window kernel when every source is a plain float / double
-    column, else the generic gather), "cols" or "generic"."""
+    width).  Returns (``dtype`` (bf16 or fp32) [n, ld] zero padded, uint8 invalid flags [n],
+    invalid count, D).  ``path``: "auto" (column-window kernel when every source is a plain
+    float / double column, else the generic gather), "cols" or "generic"."""
+    if dtype not in OUT_DTYPES:
+        raise TypeError(f"assemble writes bf16 or fp32 rows, not {dtype}")
+    out_f32 = int(dtype == torch.float32)
     if not sources or len(sources) > MAX_SOURCES:
         raise ValueError(f"assemble needs 1..{MAX_SOURCES} source columns")
     recs = np.zeros(len(sources), dtype=_SRC)
@@ -57,7 +67,7 @@ def assemble_bf16(sources, n: int, device, path: str = "auto"):
     lib = N.kernels()
     assert lib.o3s_assemble_src_size() == _SRC.itemsize
     src_d, map_d = N.upload_many(device, recs.view(np.uint8), np.asarray(colmap, dtype=np.int32).reshape(-1))
-    out = torch.empty((n, ld), dtype=torch.bfloat16, device=device)
+    out = torch.empty((n, ld), dtype=dtype, device=device)
     bad = torch.empty(n, dtype=torch.uint8, device=device)
     nbad = torch.zeros(1, dtype=torch.int32, device=device)
     cols = path == "cols" or (path == "auto" and _cols_ok(sources))
@@ -68,12 +78,12 @@ def assemble_bf16(sources, n: int, device, path: str = "auto"):
         grid = max(1, min(N.num_cus(torch.device(device)) * per_cu * 2, -(-n // rows)))
         if grid >= 8:
             grid -= grid % 8          # the kernel's XCD-aware block walk wants G % 8 == 0
-        N.check(lib.o3s_assemble_cols(src_d.data_ptr(), _DT[sources[0][0].dtype], D, ld, n, out.data_ptr(), 0,
+        N.check(lib.o3s_assemble_cols(src_d.data_ptr(), _DT[sources[0][0].dtype], D, ld, n, out.data_ptr(), out_f32,
                                       bad.data_ptr(), nbad.data_ptr(), grid, N.stream_of(out)), "assemble_cols")
         del keep
         return out, bad, nbad, D
     grid = max(1, min(N.num_cus(torch.device(device)) * 8, -(-n // 64)))
-    N.check(lib.o3s_assemble(src_d.data_ptr(), len(sources), map_d.data_ptr(), D, ld, n, out.data_ptr(), 0,
+    N.check(lib.o3s_assemble(src_d.data_ptr(), len(sources), map_d.data_ptr(), D, ld, n, out.data_ptr(), out_f32,
                              bad.data_ptr(), nbad.data_ptr(), grid, N.stream_of(out)), "assemble")
     del keep
     return out, bad, nbad, D

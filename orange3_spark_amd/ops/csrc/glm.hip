@@ -1628,4 +1628,582 @@ O3S_API int o3s_glm_softmax(const void* X, int64_t n, int64_t ldx, int d, const 
   return 0;
 }
 
+// ---------------------------------------------------------------------------------
+// fp32 feature rows (o3s.vector.dtype=float32): the same passes over X = float [n, ld]
+// (ld % 8 == 0, zero padded).  An 8-column chunk is 32 B, two 16-B loads per lane; the lane
+// -> column mapping, the slab layout and the fp64 finish are those of the mixed pass above
+// (pick_lpr / pick_cpl with the lpr_s / cpl_s remap), so o3s_glm_layout, the workspace, the
+// SGD update kernels and a captured DeviceSGD step serve both dtypes.  fp32 rows never have
+// lineage rows (lineage storage is bf16): one plain streaming tile walk per kernel.
+namespace {
+
+// One 8-column chunk of row `rowc` (both clamped by the caller): loads are unconditional,
+// the caller masks in registers (see glm_grad_kernel).
+__device__ __forceinline__ void load_chunk_f32(const float* __restrict__ X, int64_t ld, int64_t rowc, int chc,
+                                               float4_& lo, float4_& hi) {
+  const float4_* p = reinterpret_cast<const float4_*>(X + rowc * ld + 8 * chc);
+  lo = __builtin_nontemporal_load(p);
+  hi = __builtin_nontemporal_load(p + 1);
+}
+
+// Gradient pass (contract of glm_grad_mixed_kernel's resident role).  The row data is held
+// once, unpacked as loaded, for the dot product and for X^T r: twice the row registers of
+// the bf16 kernel, so UNROLL / MW are chosen per layout (launch_grad_f32) to stay out of
+// scratch.
+template <int LPR, int CPL, int UNROLL, int LOSS, int MW, bool SMP>
+__global__ __launch_bounds__(kBlock, MW) void glm_grad_f32_kernel(
+    const float* __restrict__ X, int64_t ld, int64_t n, const float* __restrict__ y, const float* __restrict__ sw,
+    const float* __restrict__ coef, const float* __restrict__ bptr, float* __restrict__ partial, int pstride,
+    int64_t res_row0, const int64_t* __restrict__ t_dev, uint32_t sseed, uint32_t sthr, int pacc) {
+  constexpr int G = kWave / LPR;
+  constexpr int RT = G * UNROLL;
+  constexpr int DP = LPR * CPL * 8;
+  using RR = RowReduce<LPR, UNROLL>;
+  constexpr int NF = RR::NF;
+  constexpr bool kDpp = LPR == 8 && UNROLL == 2;
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wid = threadIdx.x / kWave;
+  const int g = lane / LPR, c = lane % LPR;
+  const int nch = (int)(ld / 8);
+  const int ubase = RR::base(c);
+  const bool rep = RR::representative(c);
+  const float intercept = *bptr;
+  const uint32_t skey = SMP ? sample_key(sseed, (uint32_t)((t_dev ? t_dev[0] : 0) + 1)) : 0u;
+  const RowSampler smp{skey, sthr, res_row0};
+
+  float w[CPL][8], acc[CPL][8];
+#pragma unroll
+  for (int k = 0; k < CPL; ++k)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int col = 8 * (c + k * LPR) + j;
+      w[k][j] = col < ld ? coef[col] : 0.f;
+      acc[k][j] = 0.f;
+    }
+  float acc_r = 0.f, acc_loss = 0.f, acc_w = 0.f;
+
+  const int64_t ntiles = (n + RT - 1) / RT;
+  const int64_t gw = (int64_t)blockIdx.x * kWavesPerBlock + wid;
+  const int64_t nw = (int64_t)gridDim.x * kWavesPerBlock;
+  for (int64_t t = gw; t < ntiles; t += nw) {
+    const int64_t base = t * RT;
+    float4_ xv[UNROLL][CPL][2];
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) {
+      const int64_t row = base + u * G + g;
+      const bool ok = row < n;
+      const int64_t rowc = ok ? row : n - 1;
+#pragma unroll
+      for (int k = 0; k < CPL; ++k) {
+        const int ch = c + k * LPR;
+        const int chc = ch < nch ? ch : nch - 1;
+        float4_ lo, hi;
+        load_chunk_f32(X, ld, rowc, chc, lo, hi);
+        const bool okc = ok && ch < nch;
+        xv[u][k][0] = okc ? lo : float4_{0.f, 0.f, 0.f, 0.f};
+        xv[u][k][1] = okc ? hi : float4_{0.f, 0.f, 0.f, 0.f};
+      }
+    }
+    float yy[NF], ww[NF];
+#pragma unroll
+    for (int j = 0; j < NF; ++j) {
+      const int64_t row = base + (ubase + j) * G + g;
+      const bool ok = row < n;
+      const int64_t rowc = ok ? row : n - 1;
+      const float yv = y[rowc];
+      const float wv = sw ? sw[rowc] : 1.f;
+      yy[j] = ok ? yv : 0.f;
+      ww[j] = ok ? wv : 0.f;
+      if constexpr (SMP) {
+        if (!smp.keep(row)) ww[j] = 0.f;
+      }
+    }
+    float dot[UNROLL];
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) {
+      // two interleaved partial sums -> v_pk_fma_f32 (one issue per two features)
+      float2_ d2 = {0.f, 0.f};
+#pragma unroll
+      for (int k = 0; k < CPL; ++k)
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+          for (int j = 0; j < 4; j += 2) {
+            const float2_ xx = {xv[u][k][h][j], xv[u][k][h][j + 1]};
+            const float2_ ww2 = {w[k][4 * h + j], w[k][4 * h + j + 1]};
+            d2 = __builtin_elementwise_fma(xx, ww2, d2);
+          }
+      dot[u] = d2.x + d2.y;
+    }
+    if constexpr (kDpp) row_reduce_8x2(dot, c);
+    else RR::run(dot, c);
+    float res[NF];
+#pragma unroll
+    for (int j = 0; j < NF; ++j) {
+      float r, l;
+      loss_terms<LOSS>(dot[j] + intercept, yy[j], ww[j], r, l);
+      res[j] = r;
+      if (rep) { acc_r += r; acc_loss += l; acc_w += ww[j]; }
+    }
+    float other = 0.f;
+    if constexpr (kDpp) other = dpp_f<kDppHalfMirror>(res[0]);   // the other row's residual
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) {
+      float r;
+      if constexpr (kDpp) r = ((c & 4) != 0) == (u == 0) ? other : res[0];
+      else r = __shfl(res[u % NF], g * LPR + RR::owner(u), kWave);
+#pragma unroll
+      for (int k = 0; k < CPL; ++k)
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) acc[k][4 * h + j] = fmaf(r, xv[u][k][h][j], acc[k][4 * h + j]);
+    }
+  }
+
+  // Sum the G row groups of the wave (lanes c, c+LPR, ...), then the 4 waves via LDS.
+#pragma unroll
+  for (int k = 0; k < CPL; ++k)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      float v = acc[k][j];
+#pragma unroll
+      for (int off = LPR; off < kWave; off <<= 1) v += __shfl_xor(v, off, kWave);
+      acc[k][j] = v;
+    }
+  acc_r = wave_sum(acc_r);
+  acc_loss = wave_sum(acc_loss);
+  acc_w = wave_sum(acc_w);
+  __shared__ float red[kWavesPerBlock][DP + 4];
+  if (lane < LPR) {
+#pragma unroll
+    for (int k = 0; k < CPL; ++k)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) red[wid][8 * (c + k * LPR) + j] = acc[k][j];
+  }
+  if (lane == 0) {
+    red[wid][DP] = acc_r;
+    red[wid][DP + 1] = acc_loss;
+    red[wid][DP + 2] = acc_w;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < DP + 3; i += kBlock) {
+    float s = 0.f;
+#pragma unroll
+    for (int q = 0; q < kWavesPerBlock; ++q) s += red[q][i];
+    float* const pp = partial + (int64_t)blockIdx.x * pstride + i;
+    *pp = pacc ? *pp + s : s;           // pacc: later slices of a split pass add in
+  }
+}
+
+// Summarizer + first-gradient pass over fp32 rows (glm_stats_mixed_kernel, resident role).
+template <int LPR, int CPL, int U, bool UNW>
+__device__ __forceinline__ void stats_tile_f32(int64_t base, int64_t n, const float* __restrict__ X, int64_t ld,
+                                               int nch, const float* __restrict__ y, const float* __restrict__ sw,
+                                               int g, int c, float2_ (&s1)[CPL][4], float2_ (&s2)[CPL][4],
+                                               float2_ (&syx)[CPL][4], float (&rsum)[3]) {
+  constexpr int G = kWave / LPR;
+  float4_ xv[U][CPL][2];
+  float yv[U], wv[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const int64_t row = base + u * G + g;
+    const bool ok = row < n;
+    const int64_t rowc = ok ? row : n - 1;
+    yv[u] = y[rowc];
+    if (UNW) {
+      wv[u] = 1.f;
+    } else {
+      const float w0 = sw ? sw[rowc] : 1.f;
+      wv[u] = ok ? w0 : 0.f;
+    }
+#pragma unroll
+    for (int k = 0; k < CPL; ++k) {
+      const int ch = c + k * LPR;
+      const int chc = ch < nch ? ch : nch - 1;
+      float4_ lo, hi;
+      load_chunk_f32(X, ld, rowc, chc, lo, hi);
+      xv[u][k][0] = ch < nch ? lo : float4_{0.f, 0.f, 0.f, 0.f};
+      xv[u][k][1] = ch < nch ? hi : float4_{0.f, 0.f, 0.f, 0.f};
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const float2_ w2 = {wv[u], wv[u]};
+    const float wy = wv[u] * yv[u];
+    const float2_ wy2 = {wy, wy};
+#pragma unroll
+    for (int k = 0; k < CPL; ++k)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float2_ xx = {xv[u][k][j / 2][2 * (j % 2)], xv[u][k][j / 2][2 * (j % 2) + 1]};
+        const float2_ wx = UNW ? xx : w2 * xx;
+        s1[k][j] += wx;
+        s2[k][j] = __builtin_elementwise_fma(wx, xx, s2[k][j]);
+        syx[k][j] = __builtin_elementwise_fma(wy2, xx, syx[k][j]);
+      }
+    if (c == 0) {
+      rsum[0] += wv[u];
+      rsum[1] += wy;
+      rsum[2] = fmaf(wy, yv[u], rsum[2]);
+    }
+  }
+}
+
+template <int LPR, int CPL, int U, int MW>
+__global__ __launch_bounds__(kBlock, MW) void glm_stats_f32_kernel(
+    const float* __restrict__ X, int64_t ld, int64_t n, const float* __restrict__ y, const float* __restrict__ sw,
+    float* __restrict__ partial, int pstride) {
+  constexpr int G = kWave / LPR;
+  constexpr int RT = G * U;
+  constexpr int DP = LPR * CPL * 8;
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wid = threadIdx.x / kWave;
+  const int g = lane / LPR, c = lane % LPR;
+  const int nch = (int)(ld / 8);
+  float2_ s1[CPL][4], s2[CPL][4], syx[CPL][4];
+#pragma unroll
+  for (int k = 0; k < CPL; ++k)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) s1[k][j] = s2[k][j] = syx[k][j] = float2_{0.f, 0.f};
+  float rsum[3] = {0.f, 0.f, 0.f};
+  const int64_t ntiles = (n + RT - 1) / RT;
+  const int64_t gw = (int64_t)blockIdx.x * kWavesPerBlock + wid;
+  const int64_t nw = (int64_t)gridDim.x * kWavesPerBlock;
+  for (int64_t t = gw; t < ntiles; t += nw) {
+    const int64_t base = t * RT;
+    if (sw == nullptr && base + RT <= n)
+      stats_tile_f32<LPR, CPL, U, true>(base, n, X, ld, nch, y, sw, g, c, s1, s2, syx, rsum);
+    else
+      stats_tile_f32<LPR, CPL, U, false>(base, n, X, ld, nch, y, sw, g, c, s1, s2, syx, rsum);
+  }
+  // fold the G row groups of the wave, then the waves through LDS in a fixed order
+  __shared__ float red[kWavesPerBlock][3 * DP + 4];
+#pragma unroll
+  for (int k = 0; k < CPL; ++k)
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        float a = s1[k][j][h], b = s2[k][j][h], e = syx[k][j][h];
+#pragma unroll
+        for (int off = LPR; off < kWave; off <<= 1) {
+          a += __shfl_xor(a, off, kWave);
+          b += __shfl_xor(b, off, kWave);
+          e += __shfl_xor(e, off, kWave);
+        }
+        const int col = 8 * (c + k * LPR) + 2 * j + h;
+        if (lane < LPR) {
+          red[wid][col] = a;
+          red[wid][DP + col] = b;
+          red[wid][2 * DP + col] = e;
+        }
+      }
+#pragma unroll
+  for (int q = 0; q < 3; ++q) {
+    const float v = wave_sum(rsum[q]);
+    if (lane == 0) red[wid][3 * DP + q] = v;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < 3 * DP + 3; i += kBlock) {
+    float s = 0.f;
+#pragma unroll
+    for (int q = 0; q < kWavesPerBlock; ++q) s += red[q][i];
+    partial[(int64_t)blockIdx.x * pstride + i] = s;
+  }
+}
+
+// margins[i] = x_i . coef + intercept over fp32 rows (glm_margin_kernel).
+template <int LPR, int CPL>
+__global__ __launch_bounds__(kBlock) void glm_margin_f32_kernel(
+    const float* __restrict__ X, int64_t ld, int64_t n, const float* __restrict__ coef, float intercept,
+    float* __restrict__ out) {
+  constexpr int G = kWave / LPR;
+  constexpr int UNROLL = CPL >= 4 ? 1 : 4 / CPL;
+  const int lane = threadIdx.x & (kWave - 1);
+  const int g = lane / LPR, c = lane % LPR;
+  const int nch = (int)(ld / 8);
+  float w[CPL][8];
+#pragma unroll
+  for (int k = 0; k < CPL; ++k)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int col = 8 * (c + k * LPR) + j;
+      w[k][j] = col < ld ? coef[col] : 0.f;
+    }
+  const int64_t gw = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
+  const int64_t nw = ((int64_t)gridDim.x * blockDim.x) / kWave;
+  const int64_t RT = (int64_t)G * UNROLL;
+  const int64_t ntiles = (n + RT - 1) / RT;
+  for (int64_t t = gw; t < ntiles; t += nw) {
+    float4_ xv[UNROLL][CPL][2];
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) {
+      const int64_t row = t * RT + u * G + g;
+      const int64_t rowc = row < n ? row : n - 1;
+#pragma unroll
+      for (int k = 0; k < CPL; ++k) {
+        const int ch = c + k * LPR;
+        const int chc = ch < nch ? ch : nch - 1;
+        float4_ lo, hi;
+        load_chunk_f32(X, ld, rowc, chc, lo, hi);
+        xv[u][k][0] = ch < nch ? lo : float4_{0.f, 0.f, 0.f, 0.f};
+        xv[u][k][1] = ch < nch ? hi : float4_{0.f, 0.f, 0.f, 0.f};
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) {
+      const int64_t row = t * RT + u * G + g;
+      float d = 0.f;
+#pragma unroll
+      for (int k = 0; k < CPL; ++k)
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) d = fmaf(xv[u][k][h][j], w[k][4 * h + j], d);
+      d = group_sum<LPR>(d);
+      if (row < n && c == 0) out[row] = d + intercept;
+    }
+  }
+}
+
+// Weighted column moments over fp32 rows (glm_colstats_kernel, SRC == 0).
+template <int LPR, int CPL>
+__global__ __launch_bounds__(kBlock) void glm_colstats_f32_kernel(
+    const float* __restrict__ X, int64_t ld, int64_t n, const float* __restrict__ sw, float* __restrict__ partial,
+    int pstride) {
+  constexpr int G = kWave / LPR;
+  constexpr int UNROLL = CPL >= 4 ? 1 : 4 / CPL;
+  constexpr int DP = LPR * CPL * 8;
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wid = threadIdx.x / kWave;
+  const int g = lane / LPR, c = lane % LPR;
+  const int nch = (int)(ld / 8);
+  float s1[CPL][8], s2[CPL][8];
+#pragma unroll
+  for (int k = 0; k < CPL; ++k)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) s1[k][j] = s2[k][j] = 0.f;
+  float sw_acc = 0.f;
+  const int64_t RT = (int64_t)G * UNROLL;
+  const int64_t ntiles = (n + RT - 1) / RT;
+  const int64_t gw = (int64_t)blockIdx.x * kWavesPerBlock + wid;
+  const int64_t nw = (int64_t)gridDim.x * kWavesPerBlock;
+  for (int64_t t = gw; t < ntiles; t += nw) {
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) {
+      const int64_t row = t * RT + u * G + g;
+      const bool ok = row < n;
+      const int64_t rowc = ok ? row : n - 1;
+      const float wv = sw ? sw[rowc] : 1.f;
+      const float w = ok ? wv : 0.f;
+#pragma unroll
+      for (int k = 0; k < CPL; ++k) {
+        const int ch = c + k * LPR;
+        const int chc = ch < nch ? ch : nch - 1;
+        float4_ xq[2];
+        load_chunk_f32(X, ld, rowc, chc, xq[0], xq[1]);
+        const float wk = ch < nch ? w : 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const float x = xq[j / 4][j % 4];
+          const float wx = wk * x;
+          s1[k][j] += wx;
+          s2[k][j] = fmaf(wx, x, s2[k][j]);
+        }
+      }
+      if (c == 0) sw_acc += w;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < CPL; ++k)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      float a = s1[k][j], b = s2[k][j];
+#pragma unroll
+      for (int off = LPR; off < kWave; off <<= 1) {
+        a += __shfl_xor(a, off, kWave);
+        b += __shfl_xor(b, off, kWave);
+      }
+      s1[k][j] = a;
+      s2[k][j] = b;
+    }
+  sw_acc = wave_sum(sw_acc);
+  // waves add into one LDS row in turn (fixed order -> deterministic)
+  __shared__ float red[2 * DP + 2];
+  for (int q = 0; q < kWavesPerBlock; ++q) {
+    if (wid == q) {
+      if (lane < LPR) {
+#pragma unroll
+        for (int k = 0; k < CPL; ++k)
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            const int i1 = 8 * (c + k * LPR) + j;
+            red[i1] = (q == 0 ? 0.f : red[i1]) + s1[k][j];
+            red[DP + i1] = (q == 0 ? 0.f : red[DP + i1]) + s2[k][j];
+          }
+      }
+      if (lane == 0) red[2 * DP] = (q == 0 ? 0.f : red[2 * DP]) + sw_acc;
+    }
+    __syncthreads();
+  }
+  for (int i = threadIdx.x; i < 2 * DP + 1; i += kBlock) partial[(int64_t)blockIdx.x * pstride + i] = red[i];
+}
+
+// Rows in flight per lane (UNROLL) and waves per SIMD asked of the register allocator (MW)
+// of the fp32 gradient pass, per chunks-per-lane: the widest layouts keep one row at a time
+// and one wave per SIMD so that w + acc + the row stay in registers.
+template <int C> struct F32Cfg { static constexpr int U = C >= 8 ? 1 : 8 / C, MW = C >= 8 ? 1 : 2; };
+
+template <int L, int C, bool SMP>
+void launch_grad_f32(int loss, int grid, hipStream_t st, const float* X, int64_t ld, int64_t n, const float* y,
+                     const float* sw, const float* coef, const float* b, float* partial, int pstride,
+                     int64_t res_row0, const int64_t* t_dev, uint32_t sseed, uint32_t sthr, int pacc) {
+  constexpr int U = F32Cfg<C>::U, MW = F32Cfg<C>::MW;
+  if (loss == LOSS_LOGISTIC)
+    hipLaunchKernelGGL((glm_grad_f32_kernel<L, C, U, LOSS_LOGISTIC, MW, SMP>), dim3(grid), dim3(kBlock), 0, st, X, ld,
+                       n, y, sw, coef, b, partial, pstride, res_row0, t_dev, sseed, sthr, pacc);
+  else if (loss == LOSS_HINGE)
+    hipLaunchKernelGGL((glm_grad_f32_kernel<L, C, U, LOSS_HINGE, MW, SMP>), dim3(grid), dim3(kBlock), 0, st, X, ld, n,
+                       y, sw, coef, b, partial, pstride, res_row0, t_dev, sseed, sthr, pacc);
+  else
+    hipLaunchKernelGGL((glm_grad_f32_kernel<L, C, U, LOSS_SQUARED, MW, SMP>), dim3(grid), dim3(kBlock), 0, st, X, ld,
+                       n, y, sw, coef, b, partial, pstride, res_row0, t_dev, sseed, sthr, pacc);
+}
+
+// (lpr_s, cpl_s) of the mixed pass for row stride ld; false when ld has no layout.
+bool f32_layout(int64_t ld, int* lpr_s, int* cpl_s, int* dpad) {
+  const int nch = (int)(ld / 8);
+  const int lpr = pick_lpr(nch), cpl = pick_cpl(nch);
+  if (ld <= 0 || ld % 8 != 0 || cpl > 16) return false;
+  *lpr_s = lpr;
+  *cpl_s = cpl;
+  if (cpl == 1 && lpr >= 16) { *lpr_s = lpr / 4; *cpl_s = 4; }
+  else if (cpl == 2) { *lpr_s = 32; *cpl_s = 4; }
+  *dpad = lpr * cpl * 8;
+  return true;
+}
+
+}  // namespace
+
+// Every layout of the fp32 passes (the mixed pass's list).
+#define O3S_F32_LAYOUTS(M) M(4, 1) M(8, 1) M(4, 4) M(8, 4) M(16, 4) M(32, 4) M(64, 4) M(64, 8) M(64, 16)
+
+// Gradient/loss pass over fp32 rows: the out / coef / partial contract of o3s_glm_grad
+// (accumulate adds into out) with the mini-batch sampler and the splits loop of
+// o3s_glm_grad_mixed.  n_lin must be 0: fp32 rows have no lineage rows.
+O3S_API int o3s_glm_grad_f32(int loss, const void* X, int64_t ld, int64_t n, const float* y, const float* sw,
+                             const float* coef, int64_t n_lin, float* partial, int grid, double* out,
+                             int accumulate, int64_t res_row0, const int64_t* t_dev, uint32_t sseed, uint32_t sthr,
+                             int splits, hipStream_t st) {
+  int lpr_s, cpl_s, dpad;
+  if (!f32_layout(ld, &lpr_s, &cpl_s, &dpad) || grid <= 0 || n < 0 || n_lin != 0) return -1;
+  const int pstride = dpad + 4;
+  const float* Xf = (const float*)X;
+  const float* b = coef + dpad;
+  const bool smp = sthr < (1u << 24);
+#define O3S_GF(L, C)                                                                                         \
+  if (!done && lpr_s == L && cpl_s == C) {                                                                   \
+    done = true;                                                                                             \
+    if (smp)                                                                                                 \
+      launch_grad_f32<L, C, true>(loss, grid, st, XS, ld, NR, YR, SWR, coef, b, partial, pstride, RR0, t_dev, \
+                                  sseed, sthr, k > 0);                                                       \
+    else                                                                                                     \
+      launch_grad_f32<L, C, false>(loss, grid, st, XS, ld, NR, YR, SWR, coef, b, partial, pstride, RR0, t_dev, \
+                                   sseed, sthr, k > 0);                                                      \
+  }
+  const int K = splits < 1 ? 1 : splits;
+  for (int k = 0; k < K; ++k) {
+    const int64_t r_lo = n * k / K, r_hi = n * (k + 1) / K;
+    const float* XS = Xf + r_lo * ld;
+    const int64_t NR = r_hi - r_lo, RR0 = res_row0 + r_lo;
+    const float* YR = y + r_lo;
+    const float* SWR = sw ? sw + r_lo : nullptr;
+    bool done = false;
+    O3S_F32_LAYOUTS(O3S_GF)
+    if (!done) return -1;
+    O3S_CHECK_LAUNCH();
+  }
+#undef O3S_GF
+  const int ncols = dpad + 3;
+  hipLaunchKernelGGL(glm_finish_kernel, dim3((ncols + 31) / 32), dim3(1024), 0, st, partial, grid, pstride, ncols,
+                     out, accumulate);
+  O3S_CHECK_LAUNCH();
+  return 0;
+}
+
+// Fused summarizer + first-gradient pass over fp32 rows: the out / partial contract of
+// o3s_glm_stats_mixed, -2 for the layouts that one has no instantiation for (ld > 2048).
+O3S_API int o3s_glm_stats_f32(const void* X, int64_t ld, int64_t n, const float* y, const float* sw, int64_t n_lin,
+                              float* partial, int grid, double* out, hipStream_t st) {
+  int lpr_s, cpl_s, dpad;
+  if (!f32_layout(ld, &lpr_s, &cpl_s, &dpad) || grid <= 0 || n < 0 || n_lin != 0) return -1;
+  const int pstride = 3 * dpad + 4;
+  const float* Xf = (const float*)X;
+  bool done = false;
+#define O3S_SF(L, C)                                                                                        \
+  if (!done && lpr_s == L && cpl_s == C) {                                                                  \
+    done = true;                                                                                            \
+    hipLaunchKernelGGL((glm_stats_f32_kernel<L, C, (C >= 4 ? 1 : 4 / C), 2>), dim3(grid), dim3(kBlock), 0, st, Xf, \
+                       ld, n, y, sw, partial, pstride);                                                     \
+  }
+  O3S_SF(4, 1) O3S_SF(8, 1) O3S_SF(4, 4) O3S_SF(8, 4) O3S_SF(16, 4) O3S_SF(32, 4) O3S_SF(64, 4)
+#undef O3S_SF
+  if (!done) return -2;
+  O3S_CHECK_LAUNCH();
+  const int ncols = 3 * dpad + 3;
+  hipLaunchKernelGGL(glm_finish_kernel, dim3((ncols + 31) / 32), dim3(1024), 0, st, partial, grid, pstride, ncols,
+                     out, 0);
+  O3S_CHECK_LAUNCH();
+  return 0;
+}
+
+O3S_API int o3s_glm_margin_f32(const void* X, int64_t ld, int64_t n, const float* coef, float intercept, float* out,
+                               int grid, hipStream_t st) {
+  int lpr_s, cpl_s, dpad;
+  if (!f32_layout(ld, &lpr_s, &cpl_s, &dpad) || grid <= 0) return -1;
+  if (n <= 0) return 0;
+  const float* Xf = (const float*)X;
+#define O3S_MF(L, C)                                                                                          \
+  if (lpr_s == L && cpl_s == C) {                                                                             \
+    hipLaunchKernelGGL((glm_margin_f32_kernel<L, C>), dim3(grid), dim3(kBlock), 0, st, Xf, ld, n, coef,       \
+                       intercept, out);                                                                       \
+    O3S_CHECK_LAUNCH();                                                                                       \
+    return 0;                                                                                                 \
+  }
+  O3S_F32_LAYOUTS(O3S_MF)
+#undef O3S_MF
+  return -1;
+}
+
+// Column moments over fp32 rows: the out / partial contract of o3s_glm_colstats.
+O3S_API int o3s_glm_colstats_f32(const void* X, int64_t ld, int64_t n, const float* sw, float* partial, int grid,
+                                 double* out, hipStream_t st) {
+  int lpr_s, cpl_s, dpad;
+  if (!f32_layout(ld, &lpr_s, &cpl_s, &dpad) || grid <= 0 || n < 0) return -1;
+  const int pstride = 2 * dpad + 2;
+  const float* Xf = (const float*)X;
+  if (n > 0) {
+    bool done = false;
+#define O3S_CF(L, C)                                                                                          \
+  if (!done && lpr_s == L && cpl_s == C) {                                                                    \
+    hipLaunchKernelGGL((glm_colstats_f32_kernel<L, C>), dim3(grid), dim3(kBlock), 0, st, Xf, ld, n, sw,       \
+                       partial, pstride);                                                                     \
+    done = true;                                                                                              \
+  }
+    O3S_F32_LAYOUTS(O3S_CF)
+#undef O3S_CF
+    if (!done) return -1;
+  } else {
+    hipMemsetAsync(partial, 0, sizeof(float) * pstride * (size_t)grid, st);
+  }
+  O3S_CHECK_LAUNCH();
+  const int ncols = 2 * dpad + 1;
+  hipLaunchKernelGGL(glm_finish_kernel, dim3((ncols + 31) / 32), dim3(1024), 0, st, partial, grid, pstride, ncols,
+                     out, 0);
+  O3S_CHECK_LAUNCH();
+  return 0;
+}
+#undef O3S_F32_LAYOUTS
+
 O3S_PRELOAD(glm)

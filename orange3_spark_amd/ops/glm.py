@@ -1,6 +1,7 @@
 """GLM streaming ops: fused gradient/loss pass, margins, synthetic row generation.
 
-GPU tensors dispatch to ``csrc/glm.hip``; CPU tensors use the PyTorch reference
+GPU tensors -- bf16 rows, or fp32 rows whose stride is a multiple of 8 (:func:`kernel_rows`)
+-- dispatch to ``csrc/glm.hip``; CPU tensors use the PyTorch reference
 implementations below (fp64 math), which also serve as the numerics oracle in the
 tests (kernel vs plain fp32/fp64 PyTorch of the same op).
 
@@ -21,8 +22,20 @@ _MASK = 0xFFFFFFFF
 
 
 def padded_width(d: int) -> int:
-    """Row stride (elements) used for bf16 feature matrices: multiple of 8 (16 B)."""
+    """Row stride (elements) of the feature matrices the kernels stream (bf16, fp32): a
+    multiple of 8, i.e. whole 16-B (bf16) / 32-B (fp32) chunks."""
     return max(8, (d + 7) // 8 * 8)
+
+
+def f32_rows(X: torch.Tensor) -> bool:
+    """fp32 rows the HIP passes take as they are: CUDA, contiguous, row stride % 8 == 0."""
+    return (X.is_cuda and X.dtype == torch.float32 and X.dim() == 2 and X.is_contiguous()
+            and X.shape[1] > 0 and X.shape[1] % 8 == 0)
+
+
+def kernel_rows(X: torch.Tensor) -> bool:
+    """Rows the HIP passes take as they are: contiguous CUDA bf16, or fp32 (:func:`f32_rows`)."""
+    return (X.is_cuda and X.dtype == torch.bfloat16 and X.is_contiguous()) or f32_rows(X)
 
 
 def layout(ld: int) -> tuple[int, int]:
@@ -178,6 +191,10 @@ class GlmWorkspace:
         self.out = torch.empty(self.dpad + 3, dtype=torch.float64, device=self.device)
 
 
+_ROWS_MSG = ("GPU GLM pass expects a contiguous bf16 feature matrix (or a contiguous fp32 one whose row "
+             "stride is a multiple of 8)")
+
+
 def glm_grad(X: torch.Tensor, y: torch.Tensor, sw: torch.Tensor | None, coef: torch.Tensor,
              intercept: float | None, loss: int, ws: GlmWorkspace | None = None,
              accumulate: bool = False) -> torch.Tensor:
@@ -191,11 +208,16 @@ def glm_grad(X: torch.Tensor, y: torch.Tensor, sw: torch.Tensor | None, coef: to
     """
     ld = X.shape[1]
     if X.is_cuda:
-        if X.dtype != torch.bfloat16 or not X.is_contiguous():
-            raise TypeError("GPU GLM pass expects a contiguous bf16 feature matrix")
+        if not kernel_rows(X):
+            raise TypeError(_ROWS_MSG)
         ws = ws or GlmWorkspace(X.device, ld)
         cf = _coef_buf(coef, ws.dpad, X.device, intercept=intercept)
         lib = N.kernels()
+        if X.dtype == torch.float32:
+            N.check(lib.o3s_glm_grad_f32(loss, X.data_ptr(), ld, X.shape[0], y.data_ptr(), N.ptr(sw),
+                                         cf.data_ptr(), 0, ws.partial.data_ptr(), ws.grid, ws.out.data_ptr(),
+                                         int(accumulate), 0, None, 0, 1 << 24, 1, N.stream_of(X)), "glm_grad_f32")
+            return ws.out
         N.check(lib.o3s_glm_grad(loss, 0, X.data_ptr(), ld, X.shape[0], y.data_ptr(),
                                  N.ptr(sw), cf.data_ptr(), 0, 0, None, 0.0,
                                  ws.partial.data_ptr(), ws.grid, ws.out.data_ptr(), int(accumulate),
@@ -295,8 +317,17 @@ def glm_grad_mixed(X: torch.Tensor, y: torch.Tensor, sw: torch.Tensor | None, n_
             keep = sample_mask(sample_seed, it, grows, fraction).to(torch.float64)
             w = keep if sw is None else sw.to(torch.float64) * keep
         return glm_grad(torch.cat([X, Xl]), y, w, coef, intercept, loss)
-    if X.dtype != torch.bfloat16 or not X.is_contiguous() or not y.is_contiguous():
-        raise TypeError("GPU GLM pass expects a contiguous bf16 feature matrix")
+    if not kernel_rows(X) or not y.is_contiguous():
+        raise TypeError(_ROWS_MSG)
+    if X.dtype == torch.float32:
+        if n_lin:
+            raise ValueError("fp32 feature rows have no lineage rows (lineage storage is bf16)")
+        cf = _coef_buf(coef, ws.dpad, ws.device, intercept=intercept)
+        N.check(N.kernels().o3s_glm_grad_f32(loss, X.data_ptr(), ld, nr, y.data_ptr(), N.ptr(sw), cf.data_ptr(),
+                                             0, ws.partial.data_ptr(), ws.grid, ws.out.data_ptr(), 0,
+                                             int(res_row0), N.ptr(t_dev), int(sample_seed) & _MASK, thr,
+                                             mix_splits(nr), N.stream_of(X)), "glm_grad_f32")
+        return ws.out
     cf = _coef_buf(coef, ws.dpad, ws.device, intercept=intercept)
     N.check(N.kernels().o3s_glm_grad_mixed(loss, X.data_ptr(), ld, nr, y.data_ptr(), N.ptr(sw),
                                            cf.data_ptr(), seed & _MASK, row0, n_lin, ws.partial.data_ptr(),
@@ -324,6 +355,15 @@ def glm_stats_mixed(X: torch.Tensor, y: torch.Tensor, sw: torch.Tensor | None, n
     pstride = 3 * dpad + 4
     partial = torch.empty(grid * pstride, dtype=torch.float32, device=X.device)
     out = torch.empty(3 * dpad + 3, dtype=torch.float64, device=X.device)
+    if f32_rows(X):
+        if n_lin:
+            raise ValueError("fp32 feature rows have no lineage rows (lineage storage is bf16)")
+        rc = N.kernels().o3s_glm_stats_f32(X.data_ptr(), ld, nr, y.data_ptr(), N.ptr(sw), 0, partial.data_ptr(),
+                                           grid, out.data_ptr(), N.stream_of(X))
+        if rc == -2:
+            return None
+        N.check(rc, "glm_stats_f32")
+        return out
     rc = N.kernels().o3s_glm_stats_mixed(X.data_ptr(), ld, nr, y.data_ptr(), N.ptr(sw), seed & _MASK, row0,
                                          n_lin, partial.data_ptr(), grid, out.data_ptr(), STATS_WAVES, N.stream_of(X))
     if rc == -2:
@@ -389,6 +429,16 @@ def glm_margin(X: torch.Tensor, coef: torch.Tensor, intercept: float) -> torch.T
         grid = N.grid_for(X.device, X.shape[0], 64)
         N.check(lib.o3s_glm_margin(X.data_ptr(), ld, X.shape[0], cf.data_ptr(), float(intercept),
                                    out.data_ptr(), grid, N.stream_of(X)), "glm_margin")
+        return out
+    if f32_rows(X):
+        dpad, _ = layout(ld)
+        cf = torch.zeros(dpad, dtype=torch.float32, device=X.device)
+        k = min(coef.shape[0], dpad)
+        cf[:k] = coef[:k].to(X.device, torch.float32)
+        out = torch.empty(X.shape[0], dtype=torch.float32, device=X.device)
+        grid = N.grid_for(X.device, X.shape[0], 64)
+        N.check(N.kernels().o3s_glm_margin_f32(X.data_ptr(), ld, X.shape[0], cf.data_ptr(), float(intercept),
+                                               out.data_ptr(), grid, N.stream_of(X)), "glm_margin_f32")
         return out
     c = coef.to(X.device, torch.float64)[:ld]
     return (X.to(torch.float64) @ c + float(intercept)).to(torch.float32)
@@ -462,6 +512,12 @@ def glm_colstats(X: torch.Tensor, sw: torch.Tensor | None = None) -> torch.Tenso
         N.check(N.kernels().o3s_glm_colstats(0, X.data_ptr(), ld, X.shape[0], N.ptr(sw), 0, 0,
                                              partial.data_ptr(), grid, out.data_ptr(), N.stream_of(X)),
                 "glm_colstats")
+        return torch.cat([out[:ld], out[dpad:dpad + ld], out[2 * dpad:]])
+    if f32_rows(X):
+        grid = N.num_cus(X.device) * 4
+        dpad, partial, out = _colstats_out(ld, X.device, grid)
+        N.check(N.kernels().o3s_glm_colstats_f32(X.data_ptr(), ld, X.shape[0], N.ptr(sw), partial.data_ptr(), grid,
+                                                 out.data_ptr(), N.stream_of(X)), "glm_colstats_f32")
         return torch.cat([out[:ld], out[dpad:dpad + ld], out[2 * dpad:]])
     Xd = X.to(torch.float64)
     w = torch.ones(X.shape[0], dtype=torch.float64, device=X.device) if sw is None else sw.to(torch.float64)
