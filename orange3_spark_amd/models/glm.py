@@ -824,10 +824,12 @@ def fit_multinomial(comm, X: torch.Tensor, y: torch.Tensor, sw, num_classes: int
                     fit_intercept=True, standardization=True, max_iter=100, tol=1e-6, chunk=1 << 21):
     """Softmax regression (Spark 'multinomial' family).
 
-    GPU, bf16 features, d <= 256, K <= 32: every objective/gradient evaluation is ONE
-    fused pass (``glm_softmax_kernel``: margins and gradient on MFMA, X read once);
-    otherwise chunked GEMMs.  Column moments: ``glm_colstats_kernel`` (bf16) or fp32
-    chunks accumulated in fp64; class weights by bincount."""
+    GPU, bf16 or fp32 features (row stride a multiple of 8), d <= 256, K <= 32: every
+    objective/gradient evaluation is ONE fused pass (``glm_softmax_kernel`` for bf16 rows,
+    ``glm_softmax_f32_kernel`` for fp32 rows: margins and gradient on MFMA, X read once);
+    otherwise chunked GEMMs.  Column moments: ``glm_colstats_kernel`` /
+    ``glm_colstats_f32_kernel`` on the padded rows, else chunks accumulated in fp64; class
+    weights by bincount."""
     dev = X.device
     n, D = X.shape
     K = num_classes
@@ -835,8 +837,9 @@ def fit_multinomial(comm, X: torch.Tensor, y: torch.Tensor, sw, num_classes: int
     yl = y.to(dev).long()
     w = torch.ones(n, dtype=Xf_dtype, device=dev) if sw is None else sw.to(dev, Xf_dtype)
     fused = G.softmax_kernel_ok(X, K) and os.environ.get("O3S_SOFTMAX_KERNEL", "1") == "1"
+    f32_kernel = fused and X.dtype == torch.float32
     # moments
-    if X.is_cuda and X.dtype == torch.bfloat16 and X.stride(1) == 1 and X.stride(0) % 8 == 0:
+    if X.is_cuda and X.dtype in (torch.bfloat16, torch.float32) and X.stride(1) == 1 and X.stride(0) % 8 == 0:
         base = torch.as_strided(X, (n, X.stride(0)), (X.stride(0), 1))     # the padded rows (zeros beyond d)
         cs = G.glm_colstats(base, None if sw is None else w.float().contiguous())
         ldp = X.stride(0)
@@ -898,22 +901,34 @@ def fit_multinomial(comm, X: torch.Tensor, y: torch.Tensor, sw, num_classes: int
         comm.all_reduce(buf)
         buf = buf.cpu().numpy()
         Gm = buf[: D * K].reshape(D, K).T * inv[None, :] / W     # [K, D]
+        gbm = buf[D * K:D * K + K] / W
+        if f32_kernel:
+            # every row's residuals sum to zero over the classes, so the class sums of the data
+            # gradient and of the intercept gradient are exactly zero.  What the fp32 pass
+            # leaves there is rounding noise, along directions in which the objective is flat
+            # (a shift of all intercepts) or held by the penalty alone; once the true gradient
+            # is below that noise L-BFGS follows it and wrecks its curvature pairs
+            Gm = Gm - Gm.mean(0, keepdims=True)
+            gbm = gbm - gbm.mean()
         f = buf[-1] / W + 0.5 * float(np.sum(pen2[None, :] * Bt * Bt))
         Gm = Gm + pen2[None, :] * Bt
         g = Gm.reshape(-1)
         if fit_intercept:
-            g = np.concatenate([g, buf[D * K:D * K + K] / W])
+            g = np.concatenate([g, gbm])
         return f, g
 
+    # fp32 kernel rows: as in the binary fit, one iteration's decrease near the optimum sinks
+    # below the fp32 rounding of the kernel's per-row losses; the line search gets that floor
+    f_noise = 2.0 ** -24 if f32_kernel else 0.0
     x0 = np.zeros(D * K + (K if fit_intercept else 0))
     if fit_intercept:
         lp = np.log(np.maximum(prior, 1e-300))
         x0[D * K:] = lp - lp.mean()
     if reg * alpha > 0:
         l1 = np.concatenate([np.tile(pen1, K), np.zeros(K if fit_intercept else 0)])
-        r = optim.owlqn(fg, x0, l1, max_iter=max_iter, tol=tol)
+        r = optim.owlqn(fg, x0, l1, max_iter=max_iter, tol=tol, f_noise=f_noise)
     else:
-        r = optim.lbfgs(fg, x0, max_iter=max_iter, tol=tol)
+        r = optim.lbfgs(fg, x0, max_iter=max_iter, tol=tol, f_noise=f_noise)
     Bt = r.x[: D * K].reshape(K, D)
     B = Bt * inv[None, :]
     b = r.x[D * K:] if fit_intercept else np.zeros(K)

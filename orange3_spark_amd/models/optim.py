@@ -155,8 +155,10 @@ def lbfgs(fg: Fn, x0: np.ndarray, max_iter: int = 100, tol: float = 1e-6, m: int
 
 
 def owlqn(fg: Fn, x0: np.ndarray, l1: np.ndarray, max_iter: int = 100, tol: float = 1e-6, m: int = 10,
-          callback=None) -> OptimResult:
-    """Orthant-wise limited-memory quasi-Newton (Andrew & Gao 2007) for f(x) + sum l1_j |x_j|."""
+          callback=None, f_noise: float = 0.0) -> OptimResult:
+    """Orthant-wise limited-memory quasi-Newton (Andrew & Gao 2007) for f(x) + sum l1_j |x_j|.
+    ``f_noise``: relative rounding noise of ``fg``'s function values (0: exact); an increase
+    below ``f_noise * |F|`` does not fail the sufficient-decrease test."""
     x = np.array(x0, dtype=np.float64)
     l1 = np.asarray(l1, dtype=np.float64)
 
@@ -206,7 +208,7 @@ def owlqn(fg: Fn, x0: np.ndarray, l1: np.ndarray, max_iter: int = 100, tol: floa
             xn[np.sign(xn) != orthant] = 0.0
             fn, gn = fg(xn)
             Fn = total(xn, fn)
-            if Fn <= F + 1e-4 * float(pg @ (xn - x)):
+            if Fn <= F + 1e-4 * float(pg @ (xn - x)) + f_noise * abs(F):
                 ok = True
                 break
             t *= 0.5

@@ -2206,4 +2206,271 @@ O3S_API int o3s_glm_colstats_f32(const void* X, int64_t ld, int64_t n, const flo
 }
 #undef O3S_F32_LAYOUTS
 
+// ---------------------------------------------------------------------------------
+// Multinomial pass over fp32 rows: the contract, MFMA layouts, slab rows and finish of
+// glm_softmax_kernel above, for X = float [n, ldx].
+//
+// gfx950 has no xf32 and its f32-input MFMA runs at 1/16 of the bf16 rate, so a row is
+// split into bf16 terms as it is consumed (v_cvt_pk_bf16_f32 of the running remainder,
+// every subtraction exact): hi + mid + lo forward, where the margins and the loss have to
+// be at fp32 level, hi + mid backward (2^-17 relative, below the two-term split of R).
+// Forward products of total order <= 2 only (X hi with the three W terms, X mid with W hi
+// and mid, X lo with W hi: 6 MFMAs per 16 dims where the bf16 kernel issues 3); backward
+// all four of (R hi, R lo) x (X hi, X mid).
+//
+// Budget.  An fp32 tile is twice the bytes of a bf16 one, so neither of the bf16 kernel's
+// two tile copies carries over: four 32-row hi + mid tiles and the W splits exceed the
+// 160 KB of LDS, and two fp32 register copies are 256 VGPRs.  Chosen here, to keep four
+// waves per CU (one per SIMD) and a whole tile of loads in flight per wave:
+//   * the forward takes its X operand straight from the registers the row was loaded into
+//     (row r, dims 8h..+8 is one lane's 32-B load) and leaves the packed hi and mid terms
+//     in them -- the same 8 registers per 16 dims;
+//   * only the backward operand goes through LDS, 16 rows (one MFMA k-step) at a time: the
+//     half-wave that holds those rows writes hi and mid, all lanes read them transposed.
+//     [2][16][XLD] is exactly the bf16 kernel's 32-row tile area, so SmLds serves both;
+//   * the next tile is prefetched by plain vector loads into a second fp32 register copy
+//     (no LDS-DMA).  With the 128 accumulator registers that is 384 of the 512 registers
+//     a lone wave per SIMD has; the bias lives in LDS and the class of an accumulator
+//     register is recomputed from the lane id so that the NB = 8 instantiation stays out
+//     of scratch (doc/performance.md has the table).
+// Chunks at or past ldx are zero-filled, rows past n are clamped and carry weight 0.
+namespace {
+
+typedef uint32_t sm_u32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 sm_bf16x2 __attribute__((ext_vector_type(2)));
+
+// Two fp32 -> one dword of two bf16 (round to nearest even: v_cvt_pk_bf16_f32), a in the low half.
+__device__ __forceinline__ uint32_t pk_bf16(float a, float b) {
+  float2_ v;
+  v[0] = a;
+  v[1] = b;
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, sm_bf16x2));
+}
+
+// 8 fp32 -> bf16 terms hi + mid + lo (each the rounding of the exact remainder so far):
+// x - (hi + mid + lo) is below 2^-25 |x|, x - (hi + mid) below 2^-17 |x|.
+__device__ __forceinline__ void split8(const float4_ a, const float4_ b, sm_bf16x8& hi, sm_bf16x8& mid,
+                                       sm_bf16x8& lo) {
+  sm_u32x4 ph, pm, pl;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const float x0 = j < 2 ? a[2 * j] : b[2 * j - 4], x1 = j < 2 ? a[2 * j + 1] : b[2 * j - 3];
+    ph[j] = pk_bf16(x0, x1);
+    const float r0 = x0 - __uint_as_float(ph[j] << 16), r1 = x1 - __uint_as_float(ph[j] & 0xffff0000u);
+    pm[j] = pk_bf16(r0, r1);
+    pl[j] = pk_bf16(r0 - __uint_as_float(pm[j] << 16), r1 - __uint_as_float(pm[j] & 0xffff0000u));
+  }
+  hi = __builtin_bit_cast(sm_bf16x8, ph);
+  mid = __builtin_bit_cast(sm_bf16x8, pm);
+  lo = __builtin_bit_cast(sm_bf16x8, pl);
+}
+
+template <int NB>
+__global__ __launch_bounds__(kSmThreads, 1) void glm_softmax_f32_kernel(
+    const float* __restrict__ X, int64_t n, int64_t ldx, const int32_t* __restrict__ y,
+    const float* __restrict__ sw, const uint16_t* __restrict__ Wsp, const float* __restrict__ bias, int K,
+    float* __restrict__ partial, int pstride) {
+  using L = SmLds<NB>;
+  constexpr int D = L::D, KS = 2 * NB, WLD = L::WLD, XLD = L::XLD, RLD = L::RLD;
+  __shared__ __attribute__((aligned(16))) uint16_t smem[L::ELEMS];
+  __shared__ __attribute__((aligned(16))) float bs[32];   // bias, -inf for the classes past K
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int r = lane & 31, h = lane >> 5;
+  uint16_t* Ws = smem;
+  uint16_t* Xs = smem + L::W_ELEMS + wid * L::WAVE_ELEMS;   // [hi, mid][16 rows][XLD]
+  uint16_t* Rs = Xs + 32 * XLD;
+
+  for (int p = threadIdx.x; p < 3 * 32 * (D / 8); p += kSmThreads) {
+    const int row = p / (D / 8), k8 = p % (D / 8);
+    *reinterpret_cast<sm_bf16x8*>(Ws + row * WLD + k8 * 8) =
+        *reinterpret_cast<const sm_bf16x8*>(Wsp + (int64_t)row * D + k8 * 8);
+  }
+  // register v of a lane's accumulator tile is class 4 h + cv(v)
+  auto cv = [](int v) { return 8 * (v >> 2) + (v & 3); };
+  if (threadIdx.x < 32) bs[threadIdx.x] = (int)threadIdx.x < K ? bias[threadIdx.x] : -INFINITY;
+  uint16_t* Rw = Rs + 4 * h * RLD + r;
+  __syncthreads();
+
+  sm_f32x16 G[NB];
+#pragma unroll
+  for (int b = 0; b < NB; ++b)
+#pragma unroll
+    for (int v = 0; v < 16; ++v) G[b][v] = 0.f;
+  float gb[16];
+#pragma unroll
+  for (int v = 0; v < 16; ++v) gb[v] = 0.f;
+  float lossacc = 0.f;
+
+  const int64_t ntiles = (n + 31) / 32;
+  const int64_t step = (int64_t)gridDim.x * kSmWaves;
+  int64_t tile = (int64_t)blockIdx.x * kSmWaves + wid;
+  float4_ xf[KS][2], xn[KS][2];
+  auto load = [&](int64_t t, float4_ (*dst)[2]) {
+    int64_t row = t * 32 + r;
+    row = row < n ? row : n - 1;
+    const float* src = X + row * ldx;
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+      const int col = ks * 16 + 8 * h;
+      if (col < ldx) {
+        dst[ks][0] = *reinterpret_cast<const float4_*>(src + col);
+        dst[ks][1] = *reinterpret_cast<const float4_*>(src + col + 4);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) dst[ks][0][j] = dst[ks][1][j] = 0.f;
+      }
+    }
+  };
+  if (tile < ntiles) load(tile, xf);
+  for (; tile < ntiles; tile += step) {
+    if (tile + step < ntiles) load(tile + step, xn);
+    const int64_t row = tile * 32 + r;
+    const bool valid = row < n;
+    const int ylh = (valid ? y[row] : -1) - 4 * h;   // label relative to this half-wave's classes
+    const float wr = valid ? (sw ? sw[row] : 1.f) : 0.f;
+    // ---- forward: margins of row r, 16 classes per lane; the hi and mid terms of the row
+    // stay in the registers the fp32 values came in, for the backward staging below
+    sm_f32x16 acc;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float4_ b4 = *reinterpret_cast<const float4_*>(bs + 8 * j + 4 * h);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) acc[4 * j + u] = b4[u];
+    }
+    sm_bf16x8 xh[KS], xm[KS];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+      sm_bf16x8 xl;
+      split8(xf[ks][0], xf[ks][1], xh[ks], xm[ks], xl);
+      const uint16_t* wp = Ws + r * WLD + ks * 16 + 8 * h;
+      const sm_bf16x8 a0 = *reinterpret_cast<const sm_bf16x8*>(wp);
+      const sm_bf16x8 a1 = *reinterpret_cast<const sm_bf16x8*>(wp + 32 * WLD);
+      const sm_bf16x8 a2 = *reinterpret_cast<const sm_bf16x8*>(wp + 64 * WLD);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, xl, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, xh[ks], acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, xm[ks], acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, xm[ks], acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, xh[ks], acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, xh[ks], acc, 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    // ---- row softmax (the two half-waves hold disjoint class subsets of row r)
+    float mx = -INFINITY;
+#pragma unroll
+    for (int v = 0; v < 16; ++v) mx = fmaxf(mx, acc[v]);
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    float se = 0.f;
+#pragma unroll
+    for (int v = 0; v < 16; ++v) se += __expf(acc[v] - mx);
+    se += __shfl_xor(se, 32, 64);
+    const float lse = mx + __logf(se);
+#pragma unroll
+    for (int v = 0; v < 16; v += 2) {
+      float rv[2];
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const bool hit = cv(v + u) == ylh;
+        rv[u] = wr * (__expf(acc[v + u] - lse) - (hit ? 1.f : 0.f));
+        gb[v + u] += rv[u];
+        if (hit) lossacc += wr * (lse - acc[v + u]);
+      }
+      const uint32_t ph = pk_bf16(rv[0], rv[1]);
+      const uint32_t pl = pk_bf16(rv[0] - __uint_as_float(ph << 16), rv[1] - __uint_as_float(ph & 0xffff0000u));
+      Rw[cv(v) * RLD] = (uint16_t)ph;
+      Rw[cv(v + 1) * RLD] = (uint16_t)(ph >> 16);
+      Rw[(32 + cv(v)) * RLD] = (uint16_t)pl;
+      Rw[(32 + cv(v + 1)) * RLD] = (uint16_t)(pl >> 16);
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+    // ---- backward: G[class][dim] += sum over the tile's rows of R[row][class] X[row][dim],
+    // 16 rows (one MFMA k-step) at a time through this wave's staging area
+    sm_bf16x8 ar[2][2];
+#pragma unroll
+    for (int rs = 0; rs < 2; ++rs)
+#pragma unroll
+      for (int s = 0; s < 2; ++s)
+        ar[rs][s] = *reinterpret_cast<const sm_bf16x8*>(Rs + (s * 32 + r) * RLD + rs * 16 + 8 * h);
+#pragma unroll
+    for (int rs = 0; rs < 2; ++rs) {
+      if ((r >> 4) == rs) {
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+          *reinterpret_cast<sm_bf16x8*>(Xs + (r & 15) * XLD + ks * 16 + 8 * h) = xh[ks];
+          *reinterpret_cast<sm_bf16x8*>(Xs + (16 + (r & 15)) * XLD + ks * 16 + 8 * h) = xm[ks];
+        }
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_wave_barrier();
+#pragma unroll
+      for (int b = 0; b < NB; ++b) {
+        sm_bf16x8 bh, bm;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          bh[q] = (short)Xs[(8 * h + q) * XLD + b * 32 + r];
+          bm[q] = (short)Xs[(16 + 8 * h + q) * XLD + b * 32 + r];
+        }
+        G[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[rs][1], bm, G[b], 0, 0, 0);
+        G[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[rs][0], bm, G[b], 0, 0, 0);
+        G[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[rs][1], bh, G[b], 0, 0, 0);
+        G[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[rs][0], bh, G[b], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    // staged reads done before the area is overwritten
+      __builtin_amdgcn_wave_barrier();
+    }
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+      xf[ks][0] = xn[ks][0];
+      xf[ks][1] = xn[ks][1];
+    }
+  }
+  // ---- this wave's slab row: [G class-major 32 x D | sum R (32) | loss]
+  float* out = partial + ((int64_t)blockIdx.x * kSmWaves + wid) * pstride;
+#pragma unroll
+  for (int b = 0; b < NB; ++b)
+#pragma unroll
+    for (int v = 0; v < 16; ++v) out[(4 * h + cv(v)) * D + b * 32 + r] = G[b][v];
+#pragma unroll
+  for (int v = 0; v < 16; ++v) {
+    float s = gb[v];
+#pragma unroll
+    for (int off = 16; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+    if (r == 0) out[32 * D + 4 * h + cv(v)] = s;
+  }
+  const float lt = wave_sum(lossacc);
+  if (lane == 0) out[32 * D + 32] = lt;
+}
+
+}  // namespace
+
+// One multinomial pass over fp32 rows: the arguments, the out / partial layout and the
+// return codes of o3s_glm_softmax with X = float [n, ldx] (ldx % 8 == 0).
+O3S_API int o3s_glm_softmax_f32(const void* X, int64_t n, int64_t ldx, int d, const int32_t* y, const float* sw,
+                                const void* Wsp, const float* bias, int K, float* partial, int grid, double* out,
+                                hipStream_t st) {
+  const int nb = (d + 31) / 32;
+  if (ldx % 8 != 0 || nb < 1 || nb > 8 || K < 1 || K > 32 || grid <= 0) return -1;
+  const int D = 32 * nb, pstride = 32 * D + 33;
+  const float* Xf = (const float*)X;
+  const uint16_t* Wh = (const uint16_t*)Wsp;
+  if (n > 0) {
+    switch (nb) {
+#define O3S_SM(NBV) \
+  case NBV: hipLaunchKernelGGL((glm_softmax_f32_kernel<NBV>), dim3(grid), dim3(kSmThreads), 0, st, Xf, n, ldx, y, \
+                               sw, Wh, bias, K, partial, pstride); break;
+      O3S_SM(1) O3S_SM(2) O3S_SM(3) O3S_SM(4) O3S_SM(5) O3S_SM(6) O3S_SM(7) O3S_SM(8)
+#undef O3S_SM
+      default: return -1;
+    }
+  } else {
+    hipMemsetAsync(partial, 0, sizeof(float) * pstride * (size_t)grid * kSmWaves, st);
+  }
+  O3S_CHECK_LAUNCH();
+  hipLaunchKernelGGL(glm_finish_kernel, dim3((pstride + 31) / 32), dim3(1024), 0, st, partial, grid * kSmWaves,
+                     pstride, pstride, out, 0);
+  O3S_CHECK_LAUNCH();
+  return 0;
+}
+
 O3S_PRELOAD(glm)

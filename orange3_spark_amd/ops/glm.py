@@ -446,15 +446,18 @@ def glm_margin(X: torch.Tensor, coef: torch.Tensor, intercept: float) -> torch.T
 
 # --------------------------------------------------------------------------- multinomial
 def softmax_kernel_ok(X: torch.Tensor, K: int) -> bool:
-    return (X.is_cuda and X.dtype == torch.bfloat16 and X.dim() == 2 and X.stride(1) == 1
+    """Rows the fused multinomial pass takes: CUDA bf16 or fp32, unit column stride and a row
+    stride that is a multiple of 8 (so also the ``[:, :d]`` view of a padded vector column)."""
+    return (X.is_cuda and X.dtype in (torch.bfloat16, torch.float32) and X.dim() == 2 and X.stride(1) == 1
             and X.stride(0) % 8 == 0 and 1 <= X.shape[1] <= 256 and 1 <= K <= 32)
 
 
 def softmax_pass(X: torch.Tensor, y: torch.Tensor, sw: torch.Tensor | None, W: torch.Tensor, b: torch.Tensor):
-    """One fused multinomial pass over the rows of X (``glm_softmax_kernel``, csrc/glm.hip).
+    """One fused multinomial pass over the rows of X (``glm_softmax_kernel`` for bf16 rows,
+    ``glm_softmax_f32_kernel`` for fp32 rows, csrc/glm.hip).
 
-    X bf16 [n, d] (row stride a multiple of 8), y int32 labels, sw fp32 weights or None,
-    W fp32 [K, d] effective coefficients, b fp32 [K].  Returns fp64 (G [K, d] = sum_i
+    X bf16 or fp32 [n, d] (row stride a multiple of 8), y int32 labels, sw fp32 weights or
+    None, W fp32 [K, d] effective coefficients, b fp32 [K].  Returns fp64 (G [K, d] = sum_i
     w_i (p_i - onehot(y_i)) x_i^T, sum_i w_i (p_i - onehot(y_i)) [K], sum_i w_i (lse_i -
     m_{i, y_i}))."""
     n, d = X.shape
@@ -475,10 +478,12 @@ def softmax_pass(X: torch.Tensor, y: torch.Tensor, sw: torch.Tensor | None, W: t
     partial = torch.empty(grid * 4 * pstride, dtype=torch.float32, device=dev)
     out = torch.empty(pstride, dtype=torch.float64, device=dev)
     yi = y if y.dtype == torch.int32 else y.to(torch.int32)
-    N.check(N.kernels().o3s_glm_softmax(X.data_ptr(), n, X.stride(0), d, yi.contiguous().data_ptr(),
-                                        N.ptr(None if sw is None else sw.float().contiguous()),
-                                        Wsp.data_ptr(), bp.data_ptr(), K, partial.data_ptr(), grid,
-                                        out.data_ptr(), N.stream_of(X)), "glm_softmax")
+    lib = N.kernels()
+    fn = lib.o3s_glm_softmax_f32 if X.dtype == torch.float32 else lib.o3s_glm_softmax
+    N.check(fn(X.data_ptr(), n, X.stride(0), d, yi.contiguous().data_ptr(),
+               N.ptr(None if sw is None else sw.float().contiguous()),
+               Wsp.data_ptr(), bp.data_ptr(), K, partial.data_ptr(), grid,
+               out.data_ptr(), N.stream_of(X)), "glm_softmax")
     return out[: 32 * D].view(32, D)[:K, :d], out[32 * D:32 * D + K], out[32 * D + 32]
 
 
