@@ -24,6 +24,8 @@
 // HBM are recomputed from lineage on every pass -- the MI355X equivalent of Spark's
 // MEMORY_ONLY caching, where evicted partitions are recomputed.  Regenerated and
 // materialised rows are bit-identical.
+#include <type_traits>
+
 #include "common.h"
 
 using namespace o3s;
@@ -147,6 +149,195 @@ struct RowReduce {
   }
 };
 
+// ---------------------------------------------------------------------------
+// Row sources.  Every tile body below is written once and instantiated per source; a
+// source owns the registers of one 8-column chunk (`chunk`), how they are filled (`load`)
+// and how they become eight floats (`unpack`).
+//   * The memory sources take CLAMPED row / chunk indices and load unconditionally; the
+//     caller masks in registers (`mask`).  A per-load `ok ? load : 0` makes hipcc branch
+//     around every load and serialise them (CDNA guide §5, "three .s-level traps" (c)).
+//   * `pin` keeps the packed registers live across the row reduction, so that X^T r unpacks
+//     them again instead of holding 8 floats per chunk (halves the VGPR footprint).  fp32
+//     rows are held unpacked, once: nothing to pin.
+//   * Lineage rows are the raw bytes b of the hash (x = b*kSynthScale + kSynthShift): the
+//     affine map is folded into the dot product (`dot`, with wshift = kSynthShift * sum w
+//     over the lane's columns) and into X^T r (`resid`: r*b/128 plus a per-lane residual
+//     sum rs, corrected once at the end).  Rows past n are harmless (their weight is 0) and
+//     columns past ld meet zero weights and are never written out: no masking.
+struct MemoryRows {
+  static constexpr bool kLineage = false;
+  __device__ static __forceinline__ float dot(float d, float) { return d; }
+  __device__ static __forceinline__ float resid(float r, float&) { return r; }
+};
+struct RowsBf16 : MemoryRows {          // bf16 [n, ld] in memory, 16-B chunks
+  using elem = uint16_t;
+  using chunk = short8;
+  __device__ static __forceinline__ void load(const elem* __restrict__ X, int64_t ld, int64_t rowc, int chc,
+                                              chunk& v) {
+    v = __builtin_nontemporal_load(reinterpret_cast<const short8*>(X + rowc * ld + 8 * chc));
+  }
+  __device__ static __forceinline__ void mask(chunk& v, bool keep) {
+    v = keep ? v : short8{0, 0, 0, 0, 0, 0, 0, 0};
+  }
+  // the predict path's form: a plain load under its own guard
+  __device__ static __forceinline__ void load_if(const elem* __restrict__ X, int64_t ld, int64_t row, int ch,
+                                                 bool ok, chunk& v) {
+    v = ok ? *reinterpret_cast<const short8*>(X + row * ld + 8 * ch) : short8{0, 0, 0, 0, 0, 0, 0, 0};
+  }
+  __device__ static __forceinline__ void unpack(const chunk& v, float (&x)[8]) { unpack8(v, x); }
+  __device__ static __forceinline__ void pin(chunk& v) { asm volatile("" : "+v"(v)); }
+};
+struct RowsF32 : MemoryRows {           // float [n, ld] in memory, 32-B chunks (two 16-B loads)
+  using elem = float;
+  struct chunk { float4_ lo, hi; };
+  __device__ static __forceinline__ void load(const elem* __restrict__ X, int64_t ld, int64_t rowc, int chc,
+                                              chunk& v) {
+    const float4_* p = reinterpret_cast<const float4_*>(X + rowc * ld + 8 * chc);
+    v.lo = __builtin_nontemporal_load(p);
+    v.hi = __builtin_nontemporal_load(p + 1);
+  }
+  __device__ static __forceinline__ void mask(chunk& v, bool keep) {
+    v.lo = keep ? v.lo : float4_{0.f, 0.f, 0.f, 0.f};
+    v.hi = keep ? v.hi : float4_{0.f, 0.f, 0.f, 0.f};
+  }
+  __device__ static __forceinline__ void load_if(const elem* __restrict__ X, int64_t ld, int64_t row, int ch,
+                                                 bool ok, chunk& v) {
+    const float4_* p = reinterpret_cast<const float4_*>(X + row * ld + 8 * ch);
+    v.lo = ok ? p[0] : float4_{0.f, 0.f, 0.f, 0.f};
+    v.hi = ok ? p[1] : float4_{0.f, 0.f, 0.f, 0.f};
+  }
+  __device__ static __forceinline__ void unpack(const chunk& v, float (&x)[8]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      x[j] = v.lo[j];
+      x[4 + j] = v.hi[j];
+    }
+  }
+  __device__ static __forceinline__ void pin(chunk&) {}
+};
+// (Two ways in: stats_tile regenerates a chunk where it is used, load(fk, ch); grad_tile
+// forms the two hash words itself and calls decode -- with the chunk index passed through
+// load, hipcc simplifies 2*ch and 2*ch+1 inside it first and the lineage hash of the mixed
+// kernel comes out with different adds and registers.)
+struct RowsLineage {                    // regenerated from the row's feature key
+  using elem = uint16_t;                // (of the X argument the tile bodies share; never read)
+  static constexpr bool kLineage = true;
+  struct chunk { float b[8]; };
+  __device__ static __forceinline__ void load(uint32_t fk, int ch, chunk& v) {
+    decode(synth_word(fk, 2 * ch), synth_word(fk, 2 * ch + 1), v);
+  }
+  __device__ static __forceinline__ void decode(uint32_t h0, uint32_t h1, chunk& v) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      v.b[j] = synth_byte(h0, j);
+      v.b[4 + j] = synth_byte(h1, j);
+    }
+  }
+  __device__ static __forceinline__ void unpack(const chunk& v, float (&x)[8]) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) x[j] = v.b[j];
+  }
+  // the feature values themselves (exact: no bf16 round trip)
+  __device__ static __forceinline__ void values(const chunk& v, float (&x)[8]) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) x[j] = fmaf(v.b[j], kSynthScale, kSynthShift);
+  }
+  __device__ static __forceinline__ void pin(chunk& v) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) asm volatile("" : "+v"(v.b[j]));
+  }
+  __device__ static __forceinline__ float dot(float d, float wshift) { return fmaf(d, kSynthScale, wshift); }
+  __device__ static __forceinline__ float resid(float r, float& rs) {
+    rs += r;
+    return r * kSynthScale;
+  }
+};
+
+template <int LOSS>
+__device__ __forceinline__ void loss_terms(float m, float yv, float wv, float& r, float& l) {
+  if (LOSS == LOSS_LOGISTIC) {
+    const float e = __expf(-fabsf(m));
+    const float inv = __builtin_amdgcn_rcpf(1.0f + e);
+    const float p = m >= 0.f ? inv : e * inv;   // sigmoid(m)
+    r = (p - yv) * wv;
+    l = wv * (fmaxf(m, 0.f) + __logf(1.0f + e) - yv * m);
+  } else if (LOSS == LOSS_HINGE) {
+    const float s = 2.f * yv - 1.f;
+    const float mg = 1.f - s * m;
+    r = mg > 0.f ? -s * wv : 0.f;
+    l = mg > 0.f ? wv * mg : 0.f;
+  } else {
+    const float e = m - yv;
+    r = e * wv;
+    l = 0.5f * wv * e * e;
+  }
+}
+
+// Coefficients of the columns lane c owns (chunks c, c + LPR, ...), zero past ld.
+template <int LPR, int CPL>
+__device__ __forceinline__ void load_coef(const float* __restrict__ coef, int64_t ld, int c, float (&w)[CPL][8]) {
+#pragma unroll
+  for (int k = 0; k < CPL; ++k)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int col = 8 * (c + k * LPR) + j;
+      w[k][j] = col < ld ? coef[col] : 0.f;
+    }
+}
+template <class T, int A, int B>
+__device__ __forceinline__ void zero(T (&a)[A][B]) {
+#pragma unroll
+  for (int k = 0; k < A; ++k)
+#pragma unroll
+    for (int j = 0; j < B; ++j) a[k][j] = T{};
+}
+
+// Block epilogue of the gradient passes: sum the G row groups of the wave (lanes c,
+// c + LPR, ...), then the 4 waves via LDS in a fixed order, into the block's slab row
+// [X^T r (DP) | sum r | loss | weight sum].  pacc: later slices of a split pass add in.
+// (The block helpers take lane / wid / c from the kernel: recomputing them from threadIdx
+// reorders the kernel's first instructions and, with them, its register allocation.)
+template <int LPR, int CPL>
+__device__ __forceinline__ void grad_epilogue(float (&acc)[CPL][8], float acc_r, float acc_loss, float acc_w,
+                                              float* __restrict__ partial, int pstride, int pacc, int lane, int wid,
+                                              int c) {
+  constexpr int DP = LPR * CPL * 8;
+#pragma unroll
+  for (int k = 0; k < CPL; ++k)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      float v = acc[k][j];
+#pragma unroll
+      for (int off = LPR; off < kWave; off <<= 1) v += __shfl_xor(v, off, kWave);
+      acc[k][j] = v;
+    }
+  acc_r = wave_sum(acc_r);
+  acc_loss = wave_sum(acc_loss);
+  acc_w = wave_sum(acc_w);
+  __shared__ float red[kWavesPerBlock][DP + 4];
+  if (lane < LPR) {
+#pragma unroll
+    for (int k = 0; k < CPL; ++k)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) red[wid][8 * (c + k * LPR) + j] = acc[k][j];
+  }
+  if (lane == 0) {
+    red[wid][DP] = acc_r;
+    red[wid][DP + 1] = acc_loss;
+    red[wid][DP + 2] = acc_w;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < DP + 3; i += kBlock) {
+    float s = 0.f;
+#pragma unroll
+    for (int q = 0; q < kWavesPerBlock; ++q) s += red[q][i];
+    float* const pp = partial + (int64_t)blockIdx.x * pstride + i;
+    *pp = pacc ? *pp + s : s;
+  }
+}
+
+// The legacy gradient pass (L-BFGS and the two-stream overlap path): one source per launch,
+// SRC == 1 draws the lineage rows' labels in-kernel from the ground truth wtrue / btrue.
 template <int LPR, int CPL, int UNROLL, int LOSS, int SRC>
 __global__ __launch_bounds__(kBlock) void glm_grad_kernel(
     const uint16_t* __restrict__ X, int64_t ld, int64_t n, const float* __restrict__ y,
@@ -155,7 +346,6 @@ __global__ __launch_bounds__(kBlock) void glm_grad_kernel(
     float* __restrict__ partial, int pstride) {
   constexpr int G = kWave / LPR;             // rows per wave-instruction
   constexpr int RT = G * UNROLL;             // rows per wave tile
-  constexpr int DP = LPR * CPL * 8;          // padded feature count
   using RR = RowReduce<LPR, UNROLL>;
   constexpr int NF = RR::NF;
   const int lane = threadIdx.x & (kWave - 1);
@@ -171,6 +361,7 @@ __global__ __launch_bounds__(kBlock) void glm_grad_kernel(
   // pre-scaled by kSynthScale and each lane's dot products start from the shift term
   // kSynthShift * sum(w over its columns); X^T r accumulates r*b/128 plus a per-lane
   // residual sum rs, corrected once at the end.
+  // (its own coefficient loop, not load_coef: it scales w and loads wtrue alongside)
   float w[CPL][8], wt[CPL][8], acc[CPL][8];
   float wshift = 0.f, wtshift = 0.f, rs = 0.f;
 #pragma unroll
@@ -276,24 +467,8 @@ __global__ __launch_bounds__(kBlock) void glm_grad_kernel(
     float res[NF];
 #pragma unroll
     for (int j = 0; j < NF; ++j) {
-      const float m = dot[j] + intercept;
       float r, l;
-      if (LOSS == LOSS_LOGISTIC) {
-        const float e = __expf(-fabsf(m));
-        const float inv = __builtin_amdgcn_rcpf(1.0f + e);
-        const float p = m >= 0.f ? inv : e * inv;   // sigmoid(m)
-        r = (p - yy[j]) * ww[j];
-        l = ww[j] * (fmaxf(m, 0.f) + __logf(1.0f + e) - yy[j] * m);
-      } else if (LOSS == LOSS_HINGE) {
-        const float s = 2.f * yy[j] - 1.f;
-        const float mg = 1.f - s * m;
-        r = mg > 0.f ? -s * ww[j] : 0.f;
-        l = mg > 0.f ? ww[j] * mg : 0.f;
-      } else {
-        const float e = m - yy[j];
-        r = e * ww[j];
-        l = 0.5f * ww[j] * e * e;
-      }
+      loss_terms<LOSS>(dot[j] + intercept, yy[j], ww[j], r, l);
       res[j] = r;
       if (rep) { acc_r += r; acc_loss += l; acc_w += ww[j]; }
     }
@@ -335,39 +510,7 @@ __global__ __launch_bounds__(kBlock) void glm_grad_kernel(
 #pragma unroll
       for (int j = 0; j < 8; ++j) acc[k][j] = fmaf(rs, kSynthShift, acc[k][j]);
   }
-  // Sum the G row groups of the wave (lanes c, c+LPR, ...), then the 4 waves via LDS.
-#pragma unroll
-  for (int k = 0; k < CPL; ++k)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float v = acc[k][j];
-#pragma unroll
-      for (int off = LPR; off < kWave; off <<= 1) v += __shfl_xor(v, off, kWave);
-      acc[k][j] = v;
-    }
-  acc_r = wave_sum(acc_r);
-  acc_loss = wave_sum(acc_loss);
-  acc_w = wave_sum(acc_w);
-
-  __shared__ float red[kWavesPerBlock][DP + 4];
-  if (lane < LPR) {
-#pragma unroll
-    for (int k = 0; k < CPL; ++k)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) red[wid][8 * (c + k * LPR) + j] = acc[k][j];
-  }
-  if (lane == 0) {
-    red[wid][DP] = acc_r;
-    red[wid][DP + 1] = acc_loss;
-    red[wid][DP + 2] = acc_w;
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < DP + 3; i += kBlock) {
-    float s = 0.f;
-#pragma unroll
-    for (int q = 0; q < kWavesPerBlock; ++q) s += red[q][i];
-    partial[(int64_t)blockIdx.x * pstride + i] = s;
-  }
+  grad_epilogue<LPR, CPL>(acc, acc_r, acc_loss, acc_w, partial, pstride, 0, lane, wid, c);
 }
 
 // ---------------------------------------------------------------------------
@@ -380,25 +523,6 @@ __global__ __launch_bounds__(kBlock) void glm_grad_kernel(
 // floor((s+1) Tl / S) > floor(s Tl / S)), so at any moment each CU holds a mix of
 // load-bound and ALU-bound waves and both roles finish together.  Both roles use the
 // same lane->column mapping (the lineage one), so they share w / acc registers.
-template <int LOSS>
-__device__ __forceinline__ void loss_terms(float m, float yv, float wv, float& r, float& l) {
-  if (LOSS == LOSS_LOGISTIC) {
-    const float e = __expf(-fabsf(m));
-    const float inv = __builtin_amdgcn_rcpf(1.0f + e);
-    const float p = m >= 0.f ? inv : e * inv;
-    r = (p - yv) * wv;
-    l = wv * (fmaxf(m, 0.f) + __logf(1.0f + e) - yv * m);
-  } else if (LOSS == LOSS_HINGE) {
-    const float s = 2.f * yv - 1.f;
-    const float mg = 1.f - s * m;
-    r = mg > 0.f ? -s * wv : 0.f;
-    l = mg > 0.f ? wv * mg : 0.f;
-  } else {
-    const float e = m - yv;
-    r = e * wv;
-    l = 0.5f * wv * e * e;
-  }
-}
 
 // Cross-lane sums for the LPR = 8, two-rows-per-lane layout without LDS traffic: the
 // quad butterflies use quad_perm DPP, the cross-quad halving row_half_mirror (lane i <->
@@ -422,10 +546,6 @@ __device__ __forceinline__ void row_reduce_8x2(float (&v)[2], int c) {
   v[0] = keep + dpp_f<kDppHalfMirror>(send);
 }
 
-// One tile of RT rows.  SRC 0: rows of X (bf16 in HBM); SRC 1: rows regenerated from
-// their lineage (raw bytes b, x = b*kSynthScale + kSynthShift, the affine map folded into
-// the dot product and a per-lane residual sum rs).  Labels / weights of both roles come
-// from the materialised label column (y, sw already offset to the role's first row).
 // Mini-batch sampling (miniBatchFraction < 1, mllib GradientDescent's per-iteration
 // `data.sample(false, fraction, seed + i)`): row r of iteration t is kept iff
 // row_key(sample_key(seed, t), global r) >> 8 < fraction * 2^24.  The mask only zeroes a
@@ -441,46 +561,39 @@ __host__ __device__ __forceinline__ uint32_t sample_key(uint32_t seed, uint32_t 
   return fmix32(seed ^ fmix32(iter * 0x9E3779B1u + 0x7F4A7C15u));
 }
 
-template <int LPR, int CPL, int UNROLL, int LOSS, int SRC, bool SMP>
-__device__ __forceinline__ void mixed_tile(
-    int64_t base, int64_t n, const uint16_t* __restrict__ X, int64_t ld, int nch,
-    const float* __restrict__ y, const float* __restrict__ sw, uint32_t seed, int64_t row0,
-    const float (&w)[CPL][8], float wshift, float intercept, int g, int c, const RowSampler smp,
-    float (&acc)[CPL][8], float& rs, float& acc_r, float& acc_loss, float& acc_w) {
+// One gradient tile of RT = G * UNROLL rows from source SRC.  Labels / weights come from
+// the materialised label column (y, sw already offset to the role's first row).
+template <class SRC, int LPR, int CPL, int UNROLL, int LOSS, bool SMP>
+__device__ __forceinline__ void grad_tile(
+    int64_t base, int64_t n, const typename SRC::elem* __restrict__ X, int64_t ld, int nch,
+    const float* __restrict__ y, const float* __restrict__ sw, uint32_t seed, int64_t row0, const float (&w)[CPL][8],
+    float wshift, float intercept, int g, int c, const RowSampler smp, float (&acc)[CPL][8], float& rs, float& acc_r,
+    float& acc_loss, float& acc_w) {
   constexpr int G = kWave / LPR;
   using RR = RowReduce<LPR, UNROLL>;
   constexpr int NF = RR::NF;
   const int ubase = RR::base(c);
   const bool rep = RR::representative(c);
-  short8 xv[UNROLL][CPL];
-  float xf[UNROLL][CPL][8];
+  typename SRC::chunk xv[UNROLL][CPL];
 #pragma unroll
   for (int u = 0; u < UNROLL; ++u) {
     const int64_t row = base + u * G + g;
     const bool ok = row < n;
     const int64_t rowc = ok ? row : n - 1;
-    if (SRC == 0) {
+    const uint32_t fk = SRC::kLineage ? feat_key(seed, row0 + row) : 0u;
 #pragma unroll
-      for (int k = 0; k < CPL; ++k) {
-        const int ch = c + k * LPR;
+    for (int k = 0; k < CPL; ++k) {
+      const int ch = c + k * LPR;
+      if constexpr (SRC::kLineage) {
+        SRC::decode(synth_word(fk, 2 * ch), synth_word(fk, 2 * ch + 1), xv[u][k]);
+      } else {
         const int chc = ch < nch ? ch : nch - 1;
-        short8 v = __builtin_nontemporal_load(reinterpret_cast<const short8*>(X + rowc * ld + 8 * chc));
-        xv[u][k] = (ok && ch < nch) ? v : short8{0, 0, 0, 0, 0, 0, 0, 0};
-      }
-    } else {
-      const uint32_t rk = feat_key(seed, row0 + row);
-#pragma unroll
-      for (int k = 0; k < CPL; ++k) {
-        const int ch = c + k * LPR;
-        const uint32_t h0 = synth_word(rk, 2 * ch), h1 = synth_word(rk, 2 * ch + 1);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          xf[u][k][j] = synth_byte(h0, j);
-          xf[u][k][4 + j] = synth_byte(h1, j);
-        }
+        SRC::load(X, ld, rowc, chc, xv[u][k]);
+        SRC::mask(xv[u][k], ok && ch < nch);
       }
     }
   }
+  // labels / weights of the rows this lane finishes
   float yy[NF], ww[NF];
 #pragma unroll
   for (int j = 0; j < NF; ++j) {
@@ -503,19 +616,14 @@ __device__ __forceinline__ void mixed_tile(
 #pragma unroll
     for (int k = 0; k < CPL; ++k) {
       float x[8];
-      if (SRC == 0) unpack8(xv[u][k], x);
-      else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) x[j] = xf[u][k][j];
-      }
+      SRC::unpack(xv[u][k], x);
 #pragma unroll
       for (int j = 0; j < 8; j += 2) {
         const float2_ xx = {x[j], x[j + 1]}, ww2 = {w[k][j], w[k][j + 1]};
         d2 = __builtin_elementwise_fma(xx, ww2, d2);
       }
     }
-    const float d = d2.x + d2.y;
-    dot[u] = SRC == 1 ? fmaf(d, kSynthScale, wshift) : d;
+    dot[u] = SRC::dot(d2.x + d2.y, wshift);
   }
   constexpr bool kDpp = LPR == 8 && UNROLL == 2;
   if constexpr (kDpp) row_reduce_8x2(dot, c);
@@ -531,13 +639,8 @@ __device__ __forceinline__ void mixed_tile(
 #pragma unroll
   for (int u = 0; u < UNROLL; ++u)
 #pragma unroll
-    for (int k = 0; k < CPL; ++k) {
-      if (SRC == 0) asm volatile("" : "+v"(xv[u][k]));
-      else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) asm volatile("" : "+v"(xf[u][k][j]));
-      }
-    }
+    for (int k = 0; k < CPL; ++k) SRC::pin(xv[u][k]);
+  // broadcast each row's residual back to its LPR lanes, accumulate X^T r
   float other = 0.f;
   if constexpr (kDpp) other = dpp_f<kDppHalfMirror>(res[0]);   // the other row's residual
 #pragma unroll
@@ -545,15 +648,11 @@ __device__ __forceinline__ void mixed_tile(
     float r;
     if constexpr (kDpp) r = ((c & 4) != 0) == (u == 0) ? other : res[0];
     else r = __shfl(res[u % NF], g * LPR + RR::owner(u), kWave);
-    if (SRC == 1) { rs += r; r *= kSynthScale; }
+    r = SRC::resid(r, rs);
 #pragma unroll
     for (int k = 0; k < CPL; ++k) {
       float x[8];
-      if (SRC == 0) unpack8(xv[u][k], x);
-      else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) x[j] = xf[u][k][j];
-      }
+      SRC::unpack(xv[u][k], x);
 #pragma unroll
       for (int j = 0; j < 8; ++j) acc[k][j] = fmaf(r, x[j], acc[k][j]);
     }
@@ -574,20 +673,21 @@ __global__ __launch_bounds__(kBlock, MW) void glm_grad_mixed_kernel(
     uint32_t sthr, int pacc) {
   constexpr int G = kWave / LPR;
   constexpr int RT = G * UNROLL;
-  constexpr int DP = LPR * CPL * 8;
-  using RR = RowReduce<LPR, UNROLL>;
   const int lane = threadIdx.x & (kWave - 1);
   const int wid = threadIdx.x / kWave;
   const int g = lane / LPR, c = lane % LPR;
   const int nch = (int)(ld / 8);
+  // read from device memory so a device-side optimizer step never syncs the host
   const float intercept = *bptr;
   // iteration t of a device-side SGD loop = t_dev + 1 (the update kernel advances it)
   // (SMP = false: the sampler is compiled out -- no hash, no extra registers)
   const uint32_t skey = SMP ? sample_key(sseed, (uint32_t)((t_dev ? t_dev[0] : 0) + 1)) : 0u;
   const RowSampler smp_res{skey, sthr, res_row0}, smp_lin{skey, sthr, row0};
 
+  // (the coefficient loop is written out, not load_coef: it also sums wshift, and even as a
+  // helper with this very loop it cost 16 B of scratch in <8,4,2,0,3,false>)
   float w[CPL][8], acc[CPL][8];
-  float wshift = 0.f, rs = 0.f;
+  float wshift = 0.f;
 #pragma unroll
   for (int k = 0; k < CPL; ++k)
 #pragma unroll
@@ -598,6 +698,7 @@ __global__ __launch_bounds__(kBlock, MW) void glm_grad_mixed_kernel(
       acc[k][j] = 0.f;
     }
   wshift *= kSynthShift;
+  float rs = 0.f;
   float acc_r = 0.f, acc_loss = 0.f, acc_w = 0.f;
 
   const int64_t Tr = (n_res + RT - 1) / RT, Tl = (n_lin + RT - 1) / RT, S = Tr + Tl;
@@ -609,13 +710,11 @@ __global__ __launch_bounds__(kBlock, MW) void glm_grad_mixed_kernel(
     const int64_t q0 = nw * Tl / S, r0 = nw * Tl - q0 * S;
     for (int64_t s = gw; s < S; s += nw) {
       if (rem + Tl >= S)
-        mixed_tile<LPR, CPL, UNROLL, LOSS, 1, SMP>(L * RT, n_lin, X, ld, nch, y_lin, sw_lin, seed, row0, w,
-                                              wshift, intercept, g, c, smp_lin, acc, rs, acc_r, acc_loss,
-                                              acc_w);
+        grad_tile<RowsLineage, LPR, CPL, UNROLL, LOSS, SMP>(L * RT, n_lin, X, ld, nch, y_lin, sw_lin, seed, row0, w, wshift,
+                                                            intercept, g, c, smp_lin, acc, rs, acc_r, acc_loss, acc_w);
       else
-        mixed_tile<LPR, CPL, UNROLL, LOSS, 0, SMP>((s - L) * RT, n_res, X, ld, nch, y, sw, seed, row0, w,
-                                              wshift, intercept, g, c, smp_res, acc, rs, acc_r, acc_loss,
-                                              acc_w);
+        grad_tile<RowsBf16, LPR, CPL, UNROLL, LOSS, SMP>((s - L) * RT, n_res, X, ld, nch, y, sw, seed, row0, w, wshift, intercept,
+                                                         g, c, smp_res, acc, rs, acc_r, acc_loss, acc_w);
       rem += r0;
       L += q0;
       if (rem >= S) { rem -= S; ++L; }
@@ -624,35 +723,8 @@ __global__ __launch_bounds__(kBlock, MW) void glm_grad_mixed_kernel(
 #pragma unroll
   for (int k = 0; k < CPL; ++k)
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float v = fmaf(rs, kSynthShift, acc[k][j]);
-#pragma unroll
-      for (int off = LPR; off < kWave; off <<= 1) v += __shfl_xor(v, off, kWave);
-      acc[k][j] = v;
-    }
-  acc_r = wave_sum(acc_r);
-  acc_loss = wave_sum(acc_loss);
-  acc_w = wave_sum(acc_w);
-  __shared__ float red[kWavesPerBlock][DP + 4];
-  if (lane < LPR) {
-#pragma unroll
-    for (int k = 0; k < CPL; ++k)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) red[wid][8 * (c + k * LPR) + j] = acc[k][j];
-  }
-  if (lane == 0) {
-    red[wid][DP] = acc_r;
-    red[wid][DP + 1] = acc_loss;
-    red[wid][DP + 2] = acc_w;
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < DP + 3; i += kBlock) {
-    float s = 0.f;
-#pragma unroll
-    for (int q = 0; q < kWavesPerBlock; ++q) s += red[q][i];
-    float* const pp = partial + (int64_t)blockIdx.x * pstride + i;
-    *pp = pacc ? *pp + s : s;           // pacc: later slices of a split pass add in
-  }
+    for (int j = 0; j < 8; ++j) acc[k][j] = fmaf(rs, kSynthShift, acc[k][j]);
+  grad_epilogue<LPR, CPL>(acc, acc_r, acc_loss, acc_w, partial, pstride, pacc, lane, wid, c);
 }
 
 // ---------------------------------------------------------------------------
@@ -663,16 +735,18 @@ __global__ __launch_bounds__(kBlock, MW) void glm_grad_mixed_kernel(
 // zero, so each row's margin is the intercept b0 and the step-1 gradient of every loss
 // is a combination of s1 and syx (logistic: sigmoid(b0) s1 - syx) -- the fit's first
 // step needs no pass of its own (models/glm.py: DeviceSGD.first_step_from_stats).
+// One tile of G * U rows from source SRC.  Lineage rows keep only the row's feature key
+// and regenerate each chunk where it is used.
 // UNW: a full tile (every row < n) of an unweighted fit -- w = 1 is folded away, which
 // drops the w*x product from every element (the pass is VALU-bound on lineage tiles).
-template <int LPR, int CPL, int SRC, bool UNW>
-__device__ __forceinline__ void stats_tile(int64_t base, int64_t n, const uint16_t* __restrict__ X, int64_t ld,
-                                           int nch, const float* __restrict__ y, const float* __restrict__ sw,
-                                           uint32_t seed, int64_t row0, int g, int c, float2_ (&s1)[CPL][4],
-                                           float2_ (&s2)[CPL][4], float2_ (&syx)[CPL][4], float (&rsum)[3]) {
+template <class SRC, int LPR, int CPL, int U, bool UNW>
+__device__ __forceinline__ void stats_tile(int64_t base, int64_t n, const typename SRC::elem* __restrict__ X,
+                                           int64_t ld, int nch, const float* __restrict__ y,
+                                           const float* __restrict__ sw, uint32_t seed, int64_t row0, int g, int c,
+                                           float2_ (&s1)[CPL][4], float2_ (&s2)[CPL][4], float2_ (&syx)[CPL][4],
+                                           float (&rsum)[3]) {
   constexpr int G = kWave / LPR;
-  constexpr int U = CPL >= 8 ? 1 : 8 / CPL;
-  short8 xv[U][CPL];
+  typename SRC::chunk xv[U][CPL];
   uint32_t fk[U];
   float yv[U], wv[U];
 #pragma unroll
@@ -687,16 +761,15 @@ __device__ __forceinline__ void stats_tile(int64_t base, int64_t n, const uint16
       const float w0 = sw ? sw[rowc] : 1.f;
       wv[u] = ok ? w0 : 0.f;
     }
-    if (SRC == 0) {
+    if constexpr (SRC::kLineage) {
+      fk[u] = feat_key(seed, row0 + rowc);
+    } else {
 #pragma unroll
       for (int k = 0; k < CPL; ++k) {
         const int ch = c + k * LPR;
-        const int chc = ch < nch ? ch : nch - 1;
-        short8 v = __builtin_nontemporal_load(reinterpret_cast<const short8*>(X + rowc * ld + 8 * chc));
-        xv[u][k] = ch < nch ? v : short8{0, 0, 0, 0, 0, 0, 0, 0};
+        SRC::load(X, ld, rowc, ch < nch ? ch : nch - 1, xv[u][k]);
+        SRC::mask(xv[u][k], ch < nch);
       }
-    } else {
-      fk[u] = feat_key(seed, row0 + rowc);
     }
   }
 #pragma unroll
@@ -707,18 +780,11 @@ __device__ __forceinline__ void stats_tile(int64_t base, int64_t n, const uint16
 #pragma unroll
     for (int k = 0; k < CPL; ++k) {
       float x[8];
-      if (SRC == 0) {
-        unpack8(xv[u][k], x);
+      if constexpr (SRC::kLineage) {
+        SRC::load(fk[u], c + k * LPR, xv[u][k]);
+        SRC::values(xv[u][k], x);
       } else {
-        // lineage rows: the feature bytes straight from the hash (x = b/128 - 255/256 is
-        // exact), no bf16 round trip
-        const int ch = c + k * LPR;
-        const uint32_t h0 = synth_word(fk[u], 2 * ch), h1 = synth_word(fk[u], 2 * ch + 1);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          x[j] = fmaf(synth_byte(h0, j), kSynthScale, kSynthShift);
-          x[4 + j] = fmaf(synth_byte(h1, j), kSynthScale, kSynthShift);
-        }
+        SRC::unpack(xv[u][k], x);
       }
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
@@ -736,54 +802,13 @@ __device__ __forceinline__ void stats_tile(int64_t base, int64_t n, const uint16
     }
   }
 }
-
-template <int LPR, int CPL, int MW>
-__global__ __launch_bounds__(kBlock, MW) void glm_stats_mixed_kernel(
-    const uint16_t* __restrict__ X, int64_t ld, int64_t n_res, const float* __restrict__ y,
-    const float* __restrict__ sw, uint32_t seed, int64_t row0, int64_t n_lin, float* __restrict__ partial,
-    int pstride) {
-  constexpr int G = kWave / LPR;
-  constexpr int U = CPL >= 8 ? 1 : 8 / CPL;
-  constexpr int RT = G * U;
+// Block epilogue of the stats passes: fold the G row groups of the wave, then the waves
+// through LDS in a fixed order, into the slab row [s1 | s2 | syx (DP each) | row sums (3)].
+template <int LPR, int CPL>
+__device__ __forceinline__ void stats_epilogue(const float2_ (&s1)[CPL][4], const float2_ (&s2)[CPL][4],
+                                               const float2_ (&syx)[CPL][4], const float (&rsum)[3],
+                                               float* __restrict__ partial, int pstride, int lane, int wid, int c) {
   constexpr int DP = LPR * CPL * 8;
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wid = threadIdx.x / kWave;
-  const int g = lane / LPR, c = lane % LPR;
-  const int nch = (int)(ld / 8);
-  const float* y_lin = y + n_res;
-  const float* sw_lin = sw ? sw + n_res : nullptr;
-  float2_ s1[CPL][4], s2[CPL][4], syx[CPL][4];
-#pragma unroll
-  for (int k = 0; k < CPL; ++k)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) s1[k][j] = s2[k][j] = syx[k][j] = float2_{0.f, 0.f};
-  float rsum[3] = {0.f, 0.f, 0.f};
-  const int64_t Tr = (n_res + RT - 1) / RT, Tl = (n_lin + RT - 1) / RT, S = Tr + Tl;
-  const int64_t gw = (int64_t)blockIdx.x * kWavesPerBlock + wid;
-  const int64_t nw = (int64_t)gridDim.x * kWavesPerBlock;
-  if (gw < S) {
-    int64_t L = gw * Tl / S, rem = gw * Tl - L * S;
-    const int64_t q0 = nw * Tl / S, r0 = nw * Tl - q0 * S;
-    for (int64_t s = gw; s < S; s += nw) {
-      if (rem + Tl >= S) {
-        const int64_t base = L * RT;
-        if (sw == nullptr && base + RT <= n_lin)
-          stats_tile<LPR, CPL, 1, true>(base, n_lin, X, ld, nch, y_lin, sw_lin, seed, row0, g, c, s1, s2, syx, rsum);
-        else
-          stats_tile<LPR, CPL, 1, false>(base, n_lin, X, ld, nch, y_lin, sw_lin, seed, row0, g, c, s1, s2, syx, rsum);
-      } else {
-        const int64_t base = (s - L) * RT;
-        if (sw == nullptr && base + RT <= n_res)
-          stats_tile<LPR, CPL, 0, true>(base, n_res, X, ld, nch, y, sw, seed, row0, g, c, s1, s2, syx, rsum);
-        else
-          stats_tile<LPR, CPL, 0, false>(base, n_res, X, ld, nch, y, sw, seed, row0, g, c, s1, s2, syx, rsum);
-      }
-      rem += r0;
-      L += q0;
-      if (rem >= S) { rem -= S; ++L; }
-    }
-  }
-  // fold the G row groups of the wave, then the waves through LDS in a fixed order
   __shared__ float red[kWavesPerBlock][3 * DP + 4];
 #pragma unroll
   for (int k = 0; k < CPL; ++k)
@@ -817,6 +842,59 @@ __global__ __launch_bounds__(kBlock, MW) void glm_stats_mixed_kernel(
     for (int q = 0; q < kWavesPerBlock; ++q) s += red[q][i];
     partial[(int64_t)blockIdx.x * pstride + i] = s;
   }
+}
+
+template <int LPR, int CPL, int MW>
+__global__ __launch_bounds__(kBlock, MW) void glm_stats_mixed_kernel(
+    const uint16_t* __restrict__ X, int64_t ld, int64_t n_res, const float* __restrict__ y,
+    const float* __restrict__ sw, uint32_t seed, int64_t row0, int64_t n_lin, float* __restrict__ partial,
+    int pstride) {
+  constexpr int G = kWave / LPR;
+  constexpr int U = CPL >= 8 ? 1 : 8 / CPL;
+  constexpr int RT = G * U;
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wid = threadIdx.x / kWave;
+  const int g = lane / LPR, c = lane % LPR;
+  const int nch = (int)(ld / 8);
+  const float* y_lin = y + n_res;
+  const float* sw_lin = sw ? sw + n_res : nullptr;
+  float2_ s1[CPL][4], s2[CPL][4], syx[CPL][4];
+#pragma unroll
+  for (int k = 0; k < CPL; ++k)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) s1[k][j] = s2[k][j] = syx[k][j] = float2_{0.f, 0.f};
+  float rsum[3] = {0.f, 0.f, 0.f};
+  const int64_t Tr = (n_res + RT - 1) / RT, Tl = (n_lin + RT - 1) / RT, S = Tr + Tl;
+  const int64_t gw = (int64_t)blockIdx.x * kWavesPerBlock + wid;
+  const int64_t nw = (int64_t)gridDim.x * kWavesPerBlock;
+  if (gw < S) {
+    int64_t L = gw * Tl / S, rem = gw * Tl - L * S;
+    const int64_t q0 = nw * Tl / S, r0 = nw * Tl - q0 * S;
+    for (int64_t s = gw; s < S; s += nw) {
+      // full tiles of an unweighted pass take the UNW body (chosen here and in
+      // glm_stats_f32_kernel, and s1 / s2 / syx zeroed by a plain loop in both: either one in a
+      // helper took glm_stats_mixed_kernel<8,4,2> from 184 to 256 VGPRs)
+      if (rem + Tl >= S) {
+        const int64_t base = L * RT;
+        if (sw == nullptr && base + RT <= n_lin)
+          stats_tile<RowsLineage, LPR, CPL, U, true>(base, n_lin, X, ld, nch, y_lin, sw_lin, seed, row0, g, c, s1,
+                                                     s2, syx, rsum);
+        else
+          stats_tile<RowsLineage, LPR, CPL, U, false>(base, n_lin, X, ld, nch, y_lin, sw_lin, seed, row0, g, c, s1,
+                                                      s2, syx, rsum);
+      } else {
+        const int64_t base = (s - L) * RT;
+        if (sw == nullptr && base + RT <= n_res)
+          stats_tile<RowsBf16, LPR, CPL, U, true>(base, n_res, X, ld, nch, y, sw, seed, row0, g, c, s1, s2, syx, rsum);
+        else
+          stats_tile<RowsBf16, LPR, CPL, U, false>(base, n_res, X, ld, nch, y, sw, seed, row0, g, c, s1, s2, syx, rsum);
+      }
+      rem += r0;
+      L += q0;
+      if (rem >= S) { rem -= S; ++L; }
+    }
+  }
+  stats_epilogue<LPR, CPL>(s1, s2, syx, rsum, partial, pstride, lane, wid, c);
 }
 
 // Materialise synthetic rows [row0, row0+n) into X (bf16) and labels y.
@@ -860,49 +938,41 @@ __global__ __launch_bounds__(kBlock) void synth_glm_kernel(
   }
 }
 
-// margins[i] = x_i . coef + intercept (model.transform / predict path).
-template <int LPR, int CPL>
-__global__ __launch_bounds__(kBlock) void glm_margin_kernel(
-    const uint16_t* __restrict__ X, int64_t ld, int64_t n, const float* __restrict__ coef,
-    float intercept, float* __restrict__ out) {
+// margins[i] = x_i . coef + intercept (model.transform / predict path), U rows in flight
+// per lane.
+template <class SRC, int LPR, int CPL, int U>
+__device__ __forceinline__ void margin_body(const typename SRC::elem* __restrict__ X, int64_t ld, int64_t n,
+                                            const float* __restrict__ coef, float intercept,
+                                            float* __restrict__ out) {
   constexpr int G = kWave / LPR;
-  constexpr int UNROLL = CPL >= 8 ? 1 : 8 / CPL;
   const int lane = threadIdx.x & (kWave - 1);
   const int g = lane / LPR, c = lane % LPR;
   const int nch = (int)(ld / 8);
   float w[CPL][8];
-#pragma unroll
-  for (int k = 0; k < CPL; ++k)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int col = 8 * (c + k * LPR) + j;
-      w[k][j] = col < ld ? coef[col] : 0.f;
-    }
+  load_coef<LPR, CPL>(coef, ld, c, w);
   const int64_t gw = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
   const int64_t nw = ((int64_t)gridDim.x * blockDim.x) / kWave;
-  const int64_t RT = (int64_t)G * UNROLL;
+  const int64_t RT = (int64_t)G * U;
   const int64_t ntiles = (n + RT - 1) / RT;
   for (int64_t t = gw; t < ntiles; t += nw) {
-    short8 xv[UNROLL][CPL];
+    typename SRC::chunk xv[U][CPL];
 #pragma unroll
-    for (int u = 0; u < UNROLL; ++u) {
+    for (int u = 0; u < U; ++u) {
       const int64_t row = t * RT + u * G + g;
 #pragma unroll
       for (int k = 0; k < CPL; ++k) {
         const int ch = c + k * LPR;
-        xv[u][k] = (row < n && ch < nch)
-                       ? *reinterpret_cast<const short8*>(X + row * ld + 8 * ch)
-                       : short8{0, 0, 0, 0, 0, 0, 0, 0};
+        SRC::load_if(X, ld, row, ch, row < n && ch < nch, xv[u][k]);
       }
     }
 #pragma unroll
-    for (int u = 0; u < UNROLL; ++u) {
+    for (int u = 0; u < U; ++u) {
       const int64_t row = t * RT + u * G + g;
       float d = 0.f;
 #pragma unroll
       for (int k = 0; k < CPL; ++k) {
         float x[8];
-        unpack8(xv[u][k], x);
+        SRC::unpack(xv[u][k], x);
 #pragma unroll
         for (int j = 0; j < 8; ++j) d = fmaf(x[j], w[k][j], d);
       }
@@ -911,14 +981,21 @@ __global__ __launch_bounds__(kBlock) void glm_margin_kernel(
     }
   }
 }
+template <int LPR, int CPL>
+__global__ __launch_bounds__(kBlock) void glm_margin_kernel(
+    const uint16_t* __restrict__ X, int64_t ld, int64_t n, const float* __restrict__ coef,
+    float intercept, float* __restrict__ out) {
+  margin_body<RowsBf16, LPR, CPL, (CPL >= 8 ? 1 : 8 / CPL)>(X, ld, n, coef, intercept, out);
+}
 
 // Weighted column moments (Spark's MultivariateOnlineSummarizer subset used by the
 // GLM solvers for standardization): per column sum(w*x), sum(w*x^2), plus sum(w).
-// Same lane layout as the gradient pass; one slab row per block, fp64 finish.
-template <int LPR, int CPL, int SRC>
-__global__ __launch_bounds__(kBlock) void glm_colstats_kernel(
-    const uint16_t* __restrict__ X, int64_t ld, int64_t n, const float* __restrict__ sw,
-    uint32_t seed, int64_t row0, float* __restrict__ partial, int pstride) {
+// Same lane layout as the gradient pass; one slab row per block, fp64 finish.  Lineage
+// rows go through their bf16 chunk (synth_chunk), as the materialised rows would.
+template <class SRC, int LPR, int CPL>
+__device__ __forceinline__ void colstats_body(const typename SRC::elem* __restrict__ X, int64_t ld, int64_t n,
+                                              const float* __restrict__ sw, uint32_t seed, int64_t row0,
+                                              float* __restrict__ partial, int pstride) {
   constexpr int G = kWave / LPR;
   constexpr int UNROLL = CPL >= 4 ? 1 : 4 / CPL;
   constexpr int DP = LPR * CPL * 8;
@@ -927,10 +1004,8 @@ __global__ __launch_bounds__(kBlock) void glm_colstats_kernel(
   const int g = lane / LPR, c = lane % LPR;
   const int nch = (int)(ld / 8);
   float s1[CPL][8], s2[CPL][8];
-#pragma unroll
-  for (int k = 0; k < CPL; ++k)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) s1[k][j] = s2[k][j] = 0.f;
+  zero(s1);
+  zero(s2);
   float sw_acc = 0.f;
   const int64_t RT = (int64_t)G * UNROLL;
   const int64_t ntiles = (n + RT - 1) / RT;
@@ -948,11 +1023,15 @@ __global__ __launch_bounds__(kBlock) void glm_colstats_kernel(
       for (int k = 0; k < CPL; ++k) {
         const int ch = c + k * LPR;
         const int chc = ch < nch ? ch : nch - 1;
-        short8 v = SRC == 0 ? __builtin_nontemporal_load(reinterpret_cast<const short8*>(X + rowc * ld + 8 * chc))
-                            : synth_chunk(feat_key(seed, row0 + rowc), chc);
-        const float wk = ch < nch ? w : 0.f;
+        const float wk = ch < nch ? w : 0.f;        // the mask is on the weight, not on the chunk
         float x[8];
-        unpack8(v, x);
+        if constexpr (SRC::kLineage) {
+          unpack8(synth_chunk(feat_key(seed, row0 + rowc), chc), x);
+        } else {
+          typename SRC::chunk v;
+          SRC::load(X, ld, rowc, chc, v);
+          SRC::unpack(v, x);
+        }
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           const float wx = wk * x[j];
@@ -996,6 +1075,13 @@ __global__ __launch_bounds__(kBlock) void glm_colstats_kernel(
     __syncthreads();
   }
   for (int i = threadIdx.x; i < 2 * DP + 1; i += kBlock) partial[(int64_t)blockIdx.x * pstride + i] = red[i];
+}
+template <int LPR, int CPL, int SRC>
+__global__ __launch_bounds__(kBlock) void glm_colstats_kernel(
+    const uint16_t* __restrict__ X, int64_t ld, int64_t n, const float* __restrict__ sw,
+    uint32_t seed, int64_t row0, float* __restrict__ partial, int pstride) {
+  colstats_body<std::conditional_t<SRC == 0, RowsBf16, RowsLineage>, LPR, CPL>(X, ld, n, sw, seed, row0, partial,
+                                                                               pstride);
 }
 
 // out[i] = sum_b partial[b][i] in fp64, fixed order (deterministic).  Block = 32
@@ -1096,48 +1182,102 @@ int pick_cpl(int nch) {
   return c;  // 2,4,8,16 (caller checks <= 16)
 }
 
-template <int LPR, int CPL, int LOSS, int SRC>
-void launch_grad(int grid, hipStream_t st, const uint16_t* X, int64_t ld, int64_t n,
-                 const float* y, const float* sw, const float* coef, const float* b, uint32_t seed,
-                 int64_t row0, const float* wt, float bt, float* partial, int pstride) {
-  // rows in flight per lane: 8 loads for the streaming pass; the lineage pass keeps
-  // fewer chunks live (its hash work, not memory latency, is the limiter)
-  constexpr int UNROLL = SRC == 1 ? (CPL >= 8 ? 1 : 8 / CPL) : (CPL == 1 ? 8 : (CPL == 2 ? 2 : 1));
-  hipLaunchKernelGGL((glm_grad_kernel<LPR, CPL, UNROLL, LOSS, SRC>), dim3(grid), dim3(kBlock), 0,
-                     st, X, ld, n, y, sw, coef, b, seed, row0, wt, bt, partial, pstride);
+// Row layout for row stride ld: (lpr, cpl) is the natural split of pick_lpr / pick_cpl.
+// The lineage pass is VALU bound and its per-row work (row key, cross-lane dot reduction,
+// residual broadcast) is replicated on every lane of a row, so the mixed, stats and fp32
+// passes use (lpr_s, cpl_s): 4x fewer lanes per row with 4x more columns each where the
+// natural split has spare lanes (same padded width dpad).
+struct Layout { int lpr, cpl, lpr_s, cpl_s, dpad; };
+bool resolve_layout(int64_t ld, Layout* l) {
+  const int nch = (int)(ld / 8);
+  const int lpr = pick_lpr(nch), cpl = pick_cpl(nch);
+  if (ld % 8 != 0 || cpl > 16) return false;
+  int lpr_s = lpr, cpl_s = cpl;
+  if (cpl == 1 && lpr >= 16) { lpr_s = lpr / 4; cpl_s = 4; }
+  else if (cpl == 2) { lpr_s = 32; cpl_s = 4; }
+  *l = Layout{lpr, cpl, lpr_s, cpl_s, lpr * cpl * 8};
+  return true;
 }
 
-template <int LOSS, int SRC>
-int dispatch_grad(int lpr, int cpl, int grid, hipStream_t st, const uint16_t* X, int64_t ld,
-                  int64_t n, const float* y, const float* sw, const float* coef, const float* b,
-                  uint32_t seed, int64_t row0, const float* wt, float bt, float* partial,
-                  int pstride) {
-#define O3S_G(L, C)                                                                         \
-  if (lpr == L && cpl == C) {                                                               \
-    launch_grad<L, C, LOSS, SRC>(grid, st, X, ld, n, y, sw, coef, b, seed, row0, wt, bt,   \
-                                 partial, pstride);                                         \
-    return 0;                                                                               \
-  }
-  if constexpr (SRC == 0) {
-    O3S_G(4, 1) O3S_G(8, 1) O3S_G(16, 1) O3S_G(32, 1) O3S_G(64, 1)
-    O3S_G(64, 2) O3S_G(64, 4) O3S_G(64, 8) O3S_G(64, 16)
-  } else {
-    O3S_G(4, 1) O3S_G(8, 1) O3S_G(4, 4) O3S_G(8, 4) O3S_G(16, 4) O3S_G(32, 4)
-    O3S_G(64, 4) O3S_G(64, 8) O3S_G(64, 16)
-  }
-#undef O3S_G
+// Every (lpr, cpl) and every (lpr_s, cpl_s) resolve_layout can return.
+#define O3S_NATURAL_LAYOUTS(M) M(4, 1) M(8, 1) M(16, 1) M(32, 1) M(64, 1) M(64, 2) M(64, 4) M(64, 8) M(64, 16)
+#define O3S_REMAPPED_LAYOUTS(M) M(4, 1) M(8, 1) M(4, 4) M(8, 4) M(16, 4) M(32, 4) M(64, 4) M(64, 8) M(64, 16)
+
+// Run-time -> compile-time dispatch: f gets each value as a std::integral_constant object,
+// which converts to its int in constant expressions (template arguments included), and
+// returns the entry point's return code.
+template <int V> using IC = std::integral_constant<int, V>;
+#define O3S_LAYOUT_CASE(L, C) \
+  if (lpr == L && cpl == C) return f(IC<L>{}, IC<C>{});
+template <class F>
+int with_natural_layout(const Layout& l, F&& f) {
+  const int lpr = l.lpr, cpl = l.cpl;
+  O3S_NATURAL_LAYOUTS(O3S_LAYOUT_CASE)
   return -1;
+}
+template <class F>
+int with_remapped_layout(const Layout& l, F&& f) {
+  const int lpr = l.lpr_s, cpl = l.cpl_s;
+  O3S_REMAPPED_LAYOUTS(O3S_LAYOUT_CASE)
+  return -1;
+}
+#undef O3S_LAYOUT_CASE
+#undef O3S_NATURAL_LAYOUTS
+#undef O3S_REMAPPED_LAYOUTS
+template <class F>
+int with_loss(int loss, F&& f) {
+  if (loss == LOSS_LOGISTIC) return f(IC<LOSS_LOGISTIC>{});
+  if (loss == LOSS_HINGE) return f(IC<LOSS_HINGE>{});
+  return f(IC<LOSS_SQUARED>{});
+}
+template <class F>
+int with_remapped_layout_and_loss(const Layout& l, int loss, F&& f) {
+  return with_remapped_layout(l, [&](auto L, auto C) {
+    return with_loss(loss, [&](auto LOSS) { return f(L, C, LOSS); });
+  });
+}
+
+template <class... P, class... A>
+void launch(void (*kernel)(P...), int grid, hipStream_t st, A... args) {
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, st, static_cast<P>(args)...);
+}
+// out[0..ncols) = (accumulate ? out : 0) + the column sums of the grid slab rows.
+int launch_finish(const float* partial, int grid, int pstride, int ncols, double* out, int accumulate,
+                  hipStream_t st) {
+  O3S_CHECK_LAUNCH();
+  hipLaunchKernelGGL(glm_finish_kernel, dim3((ncols + 31) / 32), dim3(1024), 0, st, partial, grid, pstride, ncols,
+                     out, accumulate);
+  O3S_CHECK_LAUNCH();
+  return 0;
+}
+
+// A gradient pass runs as `splits` launches over consecutive 1/splits slices of the
+// resident and of the lineage rows; later slices add their block sums into the first
+// slice's slabs (pacc; slice order fixed: as deterministic as one launch).  A grid-stride
+// tile walk drifts over a long launch -- waves that started together end up gigabytes
+// apart, so the resident stream touches a wider address window; restarting the walk every
+// 1/splits of a 255 GB table measured 44.2 -> 43.7 ms even with a finish per slice
+// (tools/bench_glm_split_ab.py).  slice(r_lo, r_n, l_lo, l_n, pacc) launches one slice.
+template <class F>
+int for_row_slices(int splits, int64_t n_res, int64_t n_lin, F&& slice) {
+  const int K = splits < 1 ? 1 : splits;
+  for (int k = 0; k < K; ++k) {
+    const int64_t r_lo = n_res * k / K, l_lo = n_lin * k / K;
+    const int rc = slice(r_lo, n_res * (k + 1) / K - r_lo, l_lo, n_lin * (k + 1) / K - l_lo, k > 0);
+    if (rc != 0) return rc;
+    O3S_CHECK_LAUNCH();
+  }
+  return 0;
 }
 
 }  // namespace
 
 // Number of fp32 slots per partial-slab row and the padded width for `ld`.
 O3S_API int o3s_glm_layout(int64_t ld, int* dpad, int* pstride) {
-  const int nch = (int)(ld / 8);
-  const int lpr = pick_lpr(nch), cpl = pick_cpl(nch);
-  if (ld % 8 != 0 || cpl > 16) return -1;
-  *dpad = lpr * cpl * 8;
-  *pstride = *dpad + 4;
+  Layout l;
+  if (!resolve_layout(ld, &l)) return -1;
+  *dpad = l.dpad;
+  *pstride = l.dpad + 4;
   return 0;
 }
 
@@ -1149,65 +1289,34 @@ O3S_API int o3s_glm_grad(int loss, int src, const void* X, int64_t ld, int64_t n
                          const float* sw, const float* coef, uint32_t seed,
                          int64_t row0, const float* wtrue, float btrue, float* partial,
                          int grid, double* out, int accumulate, hipStream_t st) {
-  const int nch = (int)(ld / 8);
-  const int lpr = pick_lpr(nch), cpl = pick_cpl(nch);
-  if (ld % 8 != 0 || cpl > 16 || grid <= 0) return -1;
-  const int dpad = lpr * cpl * 8, pstride = dpad + 4;
+  Layout l;
+  if (!resolve_layout(ld, &l) || grid <= 0) return -1;
+  const int pstride = l.dpad + 4;
   const uint16_t* Xh = (const uint16_t*)X;
-  int rc = -1;
-  // The lineage pass is VALU bound and its per-row work (row key, cross-lane dot
-  // reduction, label draw, residual broadcast) is replicated on every lane of a row,
-  // so it uses 4x fewer lanes per row with 4x more columns each (same padded width).
-  int lpr_s = lpr, cpl_s = cpl;
-  if (cpl == 1 && lpr >= 16) { lpr_s = lpr / 4; cpl_s = 4; }
-  else if (cpl == 2) { lpr_s = 32; cpl_s = 4; }
   if (n > 0) {
-    if (src == 0) {
-      if (loss == LOSS_LOGISTIC)
-        rc = dispatch_grad<LOSS_LOGISTIC, 0>(lpr, cpl, grid, st, Xh, ld, n, y, sw, coef, coef + dpad, seed, row0, wtrue, btrue, partial, pstride);
-      else if (loss == LOSS_HINGE)
-        rc = dispatch_grad<LOSS_HINGE, 0>(lpr, cpl, grid, st, Xh, ld, n, y, sw, coef, coef + dpad, seed, row0, wtrue, btrue, partial, pstride);
-      else
-        rc = dispatch_grad<LOSS_SQUARED, 0>(lpr, cpl, grid, st, Xh, ld, n, y, sw, coef, coef + dpad, seed, row0, wtrue, btrue, partial, pstride);
-    } else {
-      if (loss == LOSS_LOGISTIC)
-        rc = dispatch_grad<LOSS_LOGISTIC, 1>(lpr_s, cpl_s, grid, st, Xh, ld, n, y, sw, coef, coef + dpad, seed, row0, wtrue, btrue, partial, pstride);
-      else if (loss == LOSS_HINGE)
-        rc = dispatch_grad<LOSS_HINGE, 1>(lpr_s, cpl_s, grid, st, Xh, ld, n, y, sw, coef, coef + dpad, seed, row0, wtrue, btrue, partial, pstride);
-      else
-        rc = dispatch_grad<LOSS_SQUARED, 1>(lpr_s, cpl_s, grid, st, Xh, ld, n, y, sw, coef, coef + dpad, seed, row0, wtrue, btrue, partial, pstride);
-    }
+    const int rc = with_loss(loss, [&](auto LOSS) {
+      // rows in flight per lane: 8 loads for the streaming pass; the lineage pass keeps
+      // fewer chunks live (its hash work, not memory latency, is the limiter)
+      if (src == 0)
+        return with_natural_layout(l, [&](auto L, auto C) {
+          constexpr int U = C == 1 ? 8 : (C == 2 ? 2 : 1);
+          launch(glm_grad_kernel<L, C, U, LOSS, 0>, grid, st, Xh, ld, n, y, sw, coef, coef + l.dpad, seed, row0,
+                 wtrue, btrue, partial, pstride);
+          return 0;
+        });
+      return with_remapped_layout(l, [&](auto L, auto C) {
+        constexpr int U = C >= 8 ? 1 : 8 / C;
+        launch(glm_grad_kernel<L, C, U, LOSS, 1>, grid, st, Xh, ld, n, y, sw, coef, coef + l.dpad, seed, row0,
+               wtrue, btrue, partial, pstride);
+        return 0;
+      });
+    });
     if (rc != 0) return rc;
   } else {
     if (accumulate) return 0;
     hipMemsetAsync(partial, 0, sizeof(float) * pstride * (size_t)grid, st);
   }
-  O3S_CHECK_LAUNCH();
-  const int ncols = dpad + 3;
-  hipLaunchKernelGGL(glm_finish_kernel, dim3((ncols + 31) / 32), dim3(1024), 0, st, partial, grid,
-                     pstride, ncols, out, accumulate);
-  O3S_CHECK_LAUNCH();
-  return 0;
-}
-
-template <int L, int C, int MW, bool SMP = false>
-static void launch_mixed(int loss, int grid, hipStream_t st, const uint16_t* X, int64_t ld, int64_t n_res,
-                         const float* y, const float* sw, const float* y_lin, const float* sw_lin, const float* coef,
-                         const float* b, uint32_t seed, int64_t row0, int64_t n_lin, float* partial, int pstride,
-                         int64_t res_row0, const int64_t* t_dev, uint32_t sseed, uint32_t sthr, int pacc) {
-  constexpr int U = C >= 8 ? 1 : 8 / C;
-  if (loss == LOSS_LOGISTIC)
-    hipLaunchKernelGGL((glm_grad_mixed_kernel<L, C, U, LOSS_LOGISTIC, MW, SMP>), dim3(grid), dim3(kBlock), 0,
-                       st, X, ld, n_res, y, sw, y_lin, sw_lin, coef, b, seed, row0, n_lin, partial, pstride,
-                       res_row0, t_dev, sseed, sthr, pacc);
-  else if (loss == LOSS_HINGE)
-    hipLaunchKernelGGL((glm_grad_mixed_kernel<L, C, U, LOSS_HINGE, MW, SMP>), dim3(grid), dim3(kBlock), 0,
-                       st, X, ld, n_res, y, sw, y_lin, sw_lin, coef, b, seed, row0, n_lin, partial, pstride,
-                       res_row0, t_dev, sseed, sthr, pacc);
-  else
-    hipLaunchKernelGGL((glm_grad_mixed_kernel<L, C, U, LOSS_SQUARED, MW, SMP>), dim3(grid), dim3(kBlock), 0,
-                       st, X, ld, n_res, y, sw, y_lin, sw_lin, coef, b, seed, row0, n_lin, partial, pstride,
-                       res_row0, t_dev, sseed, sthr, pacc);
+  return launch_finish(partial, grid, pstride, l.dpad + 3, out, accumulate, st);
 }
 
 // Mixed resident + lineage pass in one launch (see glm_grad_mixed_kernel): n_res rows
@@ -1216,108 +1325,64 @@ static void launch_mixed(int loss, int grid, hipStream_t st, const uint16_t* X, 
 // contract as o3s_glm_grad (out is overwritten).  waves: 3 asks the register allocator
 // for 3 waves/SIMD (see glm_grad_mixed_kernel), anything else 2.  Mini-batch sampling: res_row0 is the global
 // index of resident row 0, t_dev (may be null = iteration 1) the device step counter,
-// sthr = fraction * 2^24 (>= 2^24: no sampling), sseed the sampling seed.
+// sthr = fraction * 2^24 (>= 2^24: no sampling), sseed the sampling seed.  splits: see
+// for_row_slices.
 O3S_API int o3s_glm_grad_mixed(int loss, const void* X, int64_t ld, int64_t n_res, const float* y,
                                const float* sw, const float* coef, uint32_t seed, int64_t row0,
                                int64_t n_lin, float* partial, int grid, double* out, int waves,
                                int64_t res_row0, const int64_t* t_dev, uint32_t sseed,
                                uint32_t sthr, int splits, hipStream_t st) {
-  const int nch = (int)(ld / 8);
-  const int lpr = pick_lpr(nch), cpl = pick_cpl(nch);
-  if (ld % 8 != 0 || cpl > 16 || grid <= 0 || n_res < 0 || n_lin < 0) return -1;
-  const int dpad = lpr * cpl * 8, pstride = dpad + 4;
-  int lpr_s = lpr, cpl_s = cpl;
-  if (cpl == 1 && lpr >= 16) { lpr_s = lpr / 4; cpl_s = 4; }
-  else if (cpl == 2) { lpr_s = 32; cpl_s = 4; }
+  Layout l;
+  if (!resolve_layout(ld, &l) || grid <= 0 || n_res < 0 || n_lin < 0) return -1;
+  const int pstride = l.dpad + 4;
   const uint16_t* Xh = (const uint16_t*)X;
-  const float* b = coef + dpad;
   const bool smp = sthr < (1u << 24);
-#define O3S_MX(L, C)                                                                                  \
-  if (!done && lpr_s == L && cpl_s == C) {                                                            \
-    done = true;                                                                                      \
-    if (waves == 3 && smp)                                                                            \
-      launch_mixed<L, C, 3, true>(loss, grid, st, XS, ld, NR, YR, SWR, YL, SWL, coef, b, seed, RL0, NL, PS,     \
-                                  pstride, RR0, t_dev, sseed, sthr, k > 0);                                     \
-    else if (waves == 3)                                                                              \
-      launch_mixed<L, C, 3>(loss, grid, st, XS, ld, NR, YR, SWR, YL, SWL, coef, b, seed, RL0, NL, PS, pstride,  \
-                            RR0, t_dev, sseed, sthr, k > 0);                                                    \
-    else if (smp)                                                                                     \
-      launch_mixed<L, C, 2, true>(loss, grid, st, XS, ld, NR, YR, SWR, YL, SWL, coef, b, seed, RL0, NL, PS,     \
-                                  pstride, RR0, t_dev, sseed, sthr, k > 0);                                     \
-    else                                                                                              \
-      launch_mixed<L, C, 2>(loss, grid, st, XS, ld, NR, YR, SWR, YL, SWL, coef, b, seed, RL0, NL, PS, pstride,  \
-                            RR0, t_dev, sseed, sthr, k > 0);                                                    \
-  }
-  // splits > 1: the pass runs as that many launches over consecutive 1/splits slices of
-  // the resident and of the lineage rows; later slices add their block sums into the
-  // first slice's slabs (slice order fixed: as deterministic as one launch).  A
-  // grid-stride tile walk drifts over a long launch -- waves that started together end up
-  // gigabytes apart, so the resident stream touches a wider address window; restarting
-  // the walk every 1/splits of a 255 GB table measured 44.2 -> 43.7 ms even with a finish
-  // per slice (tools/bench_glm_split_ab.py).
-  const int K = splits < 1 ? 1 : splits;
-  for (int k = 0; k < K; ++k) {
-    const int64_t r_lo = n_res * k / K, r_hi = n_res * (k + 1) / K;
-    const int64_t l_lo = n_lin * k / K, l_hi = n_lin * (k + 1) / K;
-    const uint16_t* XS = Xh + r_lo * ld;
-    const int64_t NR = r_hi - r_lo, NL = l_hi - l_lo, RL0 = row0 + l_lo, RR0 = res_row0 + r_lo;
-    const float* YR = y + r_lo;
-    const float* SWR = sw ? sw + r_lo : nullptr;
-    const float* YL = y + n_res + l_lo;
-    const float* SWL = sw ? sw + n_res + l_lo : nullptr;
-    float* PS = partial;                 // slices after the first add into the same slabs
-    bool done = false;
-    O3S_MX(4, 1) O3S_MX(8, 1) O3S_MX(4, 4) O3S_MX(8, 4) O3S_MX(16, 4) O3S_MX(32, 4)
-    O3S_MX(64, 4) O3S_MX(64, 8) O3S_MX(64, 16)
-    if (!done) return -1;
-    O3S_CHECK_LAUNCH();
-  }
-#undef O3S_MX
-  const int ncols = dpad + 3;
-  hipLaunchKernelGGL(glm_finish_kernel, dim3((ncols + 31) / 32), dim3(1024), 0, st, partial, grid,
-                     pstride, ncols, out, 0);
-  O3S_CHECK_LAUNCH();
-  return 0;
+  const int rc = for_row_slices(splits, n_res, n_lin, [&](int64_t r_lo, int64_t r_n, int64_t l_lo, int64_t l_n,
+                                                           int pacc) {
+    const float* y_lin = y + n_res + l_lo;
+    const float* sw_lin = sw ? sw + n_res + l_lo : nullptr;
+    return with_remapped_layout_and_loss(l, loss, [&](auto L, auto C, auto LOSS) {
+      constexpr int U = C >= 8 ? 1 : 8 / C;
+      auto go = [&](auto MW, auto SMP) {
+        launch(glm_grad_mixed_kernel<L, C, U, LOSS, MW, SMP>, grid, st, Xh + r_lo * ld, ld, r_n, y + r_lo,
+               sw ? sw + r_lo : nullptr, y_lin, sw_lin, coef, coef + l.dpad, seed, row0 + l_lo, l_n, partial, pstride,
+               res_row0 + r_lo, t_dev, sseed, sthr, pacc);
+      };
+      if (waves == 3 && smp) go(IC<3>{}, std::true_type{});
+      else if (waves == 3) go(IC<3>{}, std::false_type{});
+      else if (smp) go(IC<2>{}, std::true_type{});
+      else go(IC<2>{}, std::false_type{});
+      return 0;
+    });
+  });
+  if (rc != 0) return rc;
+  return launch_finish(partial, grid, pstride, l.dpad + 3, out, 0, st);
 }
 
 O3S_API int o3s_synth_glm(void* X, int64_t ld, int64_t n, float* y, uint32_t seed, int64_t row0,
                           const float* wtrue, float btrue, int grid, hipStream_t st) {
-  const int nch = (int)(ld / 8);
-  const int lpr = pick_lpr(nch), cpl = pick_cpl(nch);
-  if (ld % 8 != 0 || cpl > 16) return -1;
+  Layout l;
+  if (!resolve_layout(ld, &l)) return -1;
   if (n <= 0) return 0;
-  uint16_t* Xh = (uint16_t*)X;
-#define O3S_S(L, C)                                                                           \
-  if (lpr == L && cpl == C) {                                                                 \
-    hipLaunchKernelGGL((synth_glm_kernel<L, C>), dim3(grid), dim3(kBlock), 0, st, Xh, ld, n, y, \
-                       seed, row0, wtrue, btrue);                                             \
-    O3S_CHECK_LAUNCH();                                                                       \
-    return 0;                                                                                 \
-  }
-  O3S_S(4, 1) O3S_S(8, 1) O3S_S(16, 1) O3S_S(32, 1) O3S_S(64, 1)
-  O3S_S(64, 2) O3S_S(64, 4) O3S_S(64, 8) O3S_S(64, 16)
-#undef O3S_S
-  return -1;
+  return with_natural_layout(l, [&](auto L, auto C) {
+    launch(synth_glm_kernel<L, C>, grid, st, (uint16_t*)X, ld, n, y, seed, row0,
+           wtrue, btrue);
+    O3S_CHECK_LAUNCH();
+    return 0;
+  });
 }
 
 O3S_API int o3s_glm_margin(const void* X, int64_t ld, int64_t n, const float* coef,
                            float intercept, float* out, int grid, hipStream_t st) {
-  const int nch = (int)(ld / 8);
-  const int lpr = pick_lpr(nch), cpl = pick_cpl(nch);
-  if (ld % 8 != 0 || cpl > 16) return -1;
+  Layout l;
+  if (!resolve_layout(ld, &l)) return -1;
   if (n <= 0) return 0;
-  const uint16_t* Xh = (const uint16_t*)X;
-#define O3S_M(L, C)                                                                            \
-  if (lpr == L && cpl == C) {                                                                  \
-    hipLaunchKernelGGL((glm_margin_kernel<L, C>), dim3(grid), dim3(kBlock), 0, st, Xh, ld, n,   \
-                       coef, intercept, out);                                                  \
-    O3S_CHECK_LAUNCH();                                                                        \
-    return 0;                                                                                  \
-  }
-  O3S_M(4, 1) O3S_M(8, 1) O3S_M(16, 1) O3S_M(32, 1) O3S_M(64, 1)
-  O3S_M(64, 2) O3S_M(64, 4) O3S_M(64, 8) O3S_M(64, 16)
-#undef O3S_M
-  return -1;
+  return with_natural_layout(l, [&](auto L, auto C) {
+    launch(glm_margin_kernel<L, C>, grid, st, (const uint16_t*)X, ld, n, coef,
+           intercept, out);
+    O3S_CHECK_LAUNCH();
+    return 0;
+  });
 }
 
 // Column moments: out (fp64, 2*dpad+1) = [sum w x | sum w x^2 | sum w].  partial must hold
@@ -1325,36 +1390,21 @@ O3S_API int o3s_glm_margin(const void* X, int64_t ld, int64_t n, const float* co
 O3S_API int o3s_glm_colstats(int src, const void* X, int64_t ld, int64_t n, const float* sw,
                              uint32_t seed, int64_t row0, float* partial, int grid, double* out,
                              hipStream_t st) {
-  const int nch = (int)(ld / 8);
-  const int lpr = pick_lpr(nch), cpl = pick_cpl(nch);
-  if (ld % 8 != 0 || cpl > 16 || grid <= 0) return -1;
-  const int dpad = lpr * cpl * 8, pstride = 2 * dpad + 2;
+  Layout l;
+  if (!resolve_layout(ld, &l) || grid <= 0) return -1;
+  const int pstride = 2 * l.dpad + 2;
   const uint16_t* Xh = (const uint16_t*)X;
   if (n > 0) {
-    bool done = false;
-#define O3S_C(L, C)                                                                            \
-  if (!done && lpr == L && cpl == C) {                                                         \
-    if (src == 0)                                                                              \
-      hipLaunchKernelGGL((glm_colstats_kernel<L, C, 0>), dim3(grid), dim3(kBlock), 0, st, Xh,   \
-                         ld, n, sw, seed, row0, partial, pstride);                             \
-    else                                                                                       \
-      hipLaunchKernelGGL((glm_colstats_kernel<L, C, 1>), dim3(grid), dim3(kBlock), 0, st, Xh,   \
-                         ld, n, sw, seed, row0, partial, pstride);                             \
-    done = true;                                                                               \
-  }
-    O3S_C(4, 1) O3S_C(8, 1) O3S_C(16, 1) O3S_C(32, 1) O3S_C(64, 1)
-    O3S_C(64, 2) O3S_C(64, 4) O3S_C(64, 8) O3S_C(64, 16)
-#undef O3S_C
-    if (!done) return -1;
+    const int rc = with_natural_layout(l, [&](auto L, auto C) {
+      if (src == 0) launch(glm_colstats_kernel<L, C, 0>, grid, st, Xh, ld, n, sw, seed, row0, partial, pstride);
+      else launch(glm_colstats_kernel<L, C, 1>, grid, st, Xh, ld, n, sw, seed, row0, partial, pstride);
+      return 0;
+    });
+    if (rc != 0) return rc;
   } else {
     hipMemsetAsync(partial, 0, sizeof(float) * pstride * (size_t)grid, st);
   }
-  O3S_CHECK_LAUNCH();
-  const int ncols = 2 * dpad + 1;
-  hipLaunchKernelGGL(glm_finish_kernel, dim3((ncols + 31) / 32), dim3(1024), 0, st, partial, grid,
-                     pstride, ncols, out, 0);
-  O3S_CHECK_LAUNCH();
-  return 0;
+  return launch_finish(partial, grid, pstride, 2 * l.dpad + 1, out, 0, st);
 }
 
 O3S_API int o3s_glm_sgd_update(const double* out, int dpad, double* bt, double* b, const double* inv_std,
@@ -1383,34 +1433,23 @@ O3S_API int o3s_glm_sgd_update_dev(const double* out, int dpad, double* bt, doub
 O3S_API int o3s_glm_stats_mixed(const void* X, int64_t ld, int64_t n_res, const float* y, const float* sw,
                                 uint32_t seed, int64_t row0, int64_t n_lin, float* partial, int grid, double* out,
                                 int waves, hipStream_t st) {
-  const int nch = (int)(ld / 8);
-  const int lpr = pick_lpr(nch), cpl = pick_cpl(nch);
-  if (ld % 8 != 0 || cpl > 16 || grid <= 0 || n_res < 0 || n_lin < 0) return -1;
-  const int dpad = lpr * cpl * 8, pstride = 3 * dpad + 4;
-  int lpr_s = lpr, cpl_s = cpl;
-  if (cpl == 1 && lpr >= 16) { lpr_s = lpr / 4; cpl_s = 4; }
-  else if (cpl == 2) { lpr_s = 32; cpl_s = 4; }
+  Layout l;
+  if (!resolve_layout(ld, &l) || grid <= 0 || n_res < 0 || n_lin < 0) return -1;
+  const int pstride = 3 * l.dpad + 4;
   const uint16_t* Xh = (const uint16_t*)X;
-  bool done = false;
-#define O3S_ST(L, C)                                                                                        \
-  if (!done && lpr_s == L && cpl_s == C) {                                                                  \
-    done = true;                                                                                            \
-    if (waves == 3)                                                                                         \
-      hipLaunchKernelGGL((glm_stats_mixed_kernel<L, C, 3>), dim3(grid), dim3(kBlock), 0, st, Xh, ld, n_res, y, \
-                         sw, seed, row0, n_lin, partial, pstride);                                          \
-    else                                                                                                    \
-      hipLaunchKernelGGL((glm_stats_mixed_kernel<L, C, 2>), dim3(grid), dim3(kBlock), 0, st, Xh, ld, n_res, y, \
-                         sw, seed, row0, n_lin, partial, pstride);                                          \
-  }
-  O3S_ST(4, 1) O3S_ST(8, 1) O3S_ST(4, 4) O3S_ST(8, 4) O3S_ST(16, 4) O3S_ST(32, 4) O3S_ST(64, 4)
-#undef O3S_ST
-  if (!done) return -2;
-  O3S_CHECK_LAUNCH();
-  const int ncols = 3 * dpad + 3;
-  hipLaunchKernelGGL(glm_finish_kernel, dim3((ncols + 31) / 32), dim3(1024), 0, st, partial, grid, pstride, ncols,
-                     out, 0);
-  O3S_CHECK_LAUNCH();
-  return 0;
+  const int rc = with_remapped_layout(l, [&](auto L, auto C) {
+    if constexpr (C > 4) {
+      return -2;
+    } else {
+      if (waves == 3)
+        launch(glm_stats_mixed_kernel<L, C, 3>, grid, st, Xh, ld, n_res, y, sw, seed, row0, n_lin, partial, pstride);
+      else
+        launch(glm_stats_mixed_kernel<L, C, 2>, grid, st, Xh, ld, n_res, y, sw, seed, row0, n_lin, partial, pstride);
+      return 0;
+    }
+  });
+  if (rc != 0) return rc;
+  return launch_finish(partial, grid, pstride, 3 * l.dpad + 3, out, 0, st);
 }
 
 // ---------------------------------------------------------------------------------
@@ -1629,27 +1668,26 @@ O3S_API int o3s_glm_softmax(const void* X, int64_t n, int64_t ldx, int d, const 
 }
 
 // ---------------------------------------------------------------------------------
-// fp32 feature rows (o3s.vector.dtype=float32): the same passes over X = float [n, ld]
-// (ld % 8 == 0, zero padded).  An 8-column chunk is 32 B, two 16-B loads per lane; the lane
-// -> column mapping, the slab layout and the fp64 finish are those of the mixed pass above
-// (pick_lpr / pick_cpl with the lpr_s / cpl_s remap), so o3s_glm_layout, the workspace, the
-// SGD update kernels and a captured DeviceSGD step serve both dtypes.  fp32 rows never have
-// lineage rows (lineage storage is bf16): one plain streaming tile walk per kernel.
+// fp32 feature rows (o3s.vector.dtype=float32): the passes above over X = float [n, ld]
+// (ld % 8 == 0, zero padded), with the RowsF32 source.  What that source changes: an
+// 8-column chunk is 32 B, two 16-B loads per lane, and the row is held once, unpacked as
+// loaded, for the dot product and for X^T r -- twice the row registers of the bf16 kernels,
+// so the rows in flight and the register budget are chosen per layout (F32Cfg) to stay out
+// of scratch.  fp32 rows never have lineage rows (lineage storage is bf16): one plain
+// streaming tile walk per kernel, no lineage code in any instantiation.  The stats, margin
+// and column-moment kernels instantiate the shared bodies; the gradient kernel keeps its own
+// tile (below).  The lane -> column
+// mapping (the remapped layouts), the slab layout and the fp64 finish are those of the mixed
+// pass, so o3s_glm_layout, the workspace, the SGD update kernels and a captured DeviceSGD
+// step serve both dtypes.
 namespace {
 
-// One 8-column chunk of row `rowc` (both clamped by the caller): loads are unconditional,
-// the caller masks in registers (see glm_grad_kernel).
-__device__ __forceinline__ void load_chunk_f32(const float* __restrict__ X, int64_t ld, int64_t rowc, int chc,
-                                               float4_& lo, float4_& hi) {
-  const float4_* p = reinterpret_cast<const float4_*>(X + rowc * ld + 8 * chc);
-  lo = __builtin_nontemporal_load(p);
-  hi = __builtin_nontemporal_load(p + 1);
-}
-
-// Gradient pass (contract of glm_grad_mixed_kernel's resident role).  The row data is held
-// once, unpacked as loaded, for the dot product and for X^T r: twice the row registers of
-// the bf16 kernel, so UNROLL / MW are chosen per layout (launch_grad_f32) to stay out of
-// scratch.
+// Gradient pass (contract of glm_grad_mixed_kernel's resident role).  It shares the row
+// source's load / mask, loss_terms, the row reduction and grad_epilogue with the other
+// gradient kernels, but NOT grad_tile: instantiated as grad_tile<RowsF32> the same statements
+// cost 2-6 VGPRs in every layout -- 3 -> 2 waves/SIMD in <4,4,2,*,true>, dot[] spilled to LDS
+// in <4,1,8> -- and hipcc contracts the weighted loss line differently (last-bit changes in
+// sum r / loss).  Written here, in the kernel, the tile keeps its registers and its bits.
 template <int LPR, int CPL, int UNROLL, int LOSS, int MW, bool SMP>
 __global__ __launch_bounds__(kBlock, MW) void glm_grad_f32_kernel(
     const float* __restrict__ X, int64_t ld, int64_t n, const float* __restrict__ y, const float* __restrict__ sw,
@@ -1657,7 +1695,6 @@ __global__ __launch_bounds__(kBlock, MW) void glm_grad_f32_kernel(
     int64_t res_row0, const int64_t* __restrict__ t_dev, uint32_t sseed, uint32_t sthr, int pacc) {
   constexpr int G = kWave / LPR;
   constexpr int RT = G * UNROLL;
-  constexpr int DP = LPR * CPL * 8;
   using RR = RowReduce<LPR, UNROLL>;
   constexpr int NF = RR::NF;
   constexpr bool kDpp = LPR == 8 && UNROLL == 2;
@@ -1671,6 +1708,7 @@ __global__ __launch_bounds__(kBlock, MW) void glm_grad_f32_kernel(
   const uint32_t skey = SMP ? sample_key(sseed, (uint32_t)((t_dev ? t_dev[0] : 0) + 1)) : 0u;
   const RowSampler smp{skey, sthr, res_row0};
 
+  // (written out, not load_coef: the helper cost 4 VGPRs in every layout of this kernel)
   float w[CPL][8], acc[CPL][8];
 #pragma unroll
   for (int k = 0; k < CPL; ++k)
@@ -1697,11 +1735,11 @@ __global__ __launch_bounds__(kBlock, MW) void glm_grad_f32_kernel(
       for (int k = 0; k < CPL; ++k) {
         const int ch = c + k * LPR;
         const int chc = ch < nch ? ch : nch - 1;
-        float4_ lo, hi;
-        load_chunk_f32(X, ld, rowc, chc, lo, hi);
-        const bool okc = ok && ch < nch;
-        xv[u][k][0] = okc ? lo : float4_{0.f, 0.f, 0.f, 0.f};
-        xv[u][k][1] = okc ? hi : float4_{0.f, 0.f, 0.f, 0.f};
+        RowsF32::chunk v;
+        RowsF32::load(X, ld, rowc, chc, v);
+        RowsF32::mask(v, ok && ch < nch);
+        xv[u][k][0] = v.lo;
+        xv[u][k][1] = v.hi;
       }
     }
     float yy[NF], ww[NF];
@@ -1761,102 +1799,15 @@ __global__ __launch_bounds__(kBlock, MW) void glm_grad_f32_kernel(
     }
   }
 
-  // Sum the G row groups of the wave (lanes c, c+LPR, ...), then the 4 waves via LDS.
-#pragma unroll
-  for (int k = 0; k < CPL; ++k)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float v = acc[k][j];
-#pragma unroll
-      for (int off = LPR; off < kWave; off <<= 1) v += __shfl_xor(v, off, kWave);
-      acc[k][j] = v;
-    }
-  acc_r = wave_sum(acc_r);
-  acc_loss = wave_sum(acc_loss);
-  acc_w = wave_sum(acc_w);
-  __shared__ float red[kWavesPerBlock][DP + 4];
-  if (lane < LPR) {
-#pragma unroll
-    for (int k = 0; k < CPL; ++k)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) red[wid][8 * (c + k * LPR) + j] = acc[k][j];
-  }
-  if (lane == 0) {
-    red[wid][DP] = acc_r;
-    red[wid][DP + 1] = acc_loss;
-    red[wid][DP + 2] = acc_w;
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < DP + 3; i += kBlock) {
-    float s = 0.f;
-#pragma unroll
-    for (int q = 0; q < kWavesPerBlock; ++q) s += red[q][i];
-    float* const pp = partial + (int64_t)blockIdx.x * pstride + i;
-    *pp = pacc ? *pp + s : s;           // pacc: later slices of a split pass add in
-  }
+  grad_epilogue<LPR, CPL>(acc, acc_r, acc_loss, acc_w, partial, pstride, pacc, lane, wid, c);
 }
 
-// Summarizer + first-gradient pass over fp32 rows (glm_stats_mixed_kernel, resident role).
-template <int LPR, int CPL, int U, bool UNW>
-__device__ __forceinline__ void stats_tile_f32(int64_t base, int64_t n, const float* __restrict__ X, int64_t ld,
-                                               int nch, const float* __restrict__ y, const float* __restrict__ sw,
-                                               int g, int c, float2_ (&s1)[CPL][4], float2_ (&s2)[CPL][4],
-                                               float2_ (&syx)[CPL][4], float (&rsum)[3]) {
-  constexpr int G = kWave / LPR;
-  float4_ xv[U][CPL][2];
-  float yv[U], wv[U];
-#pragma unroll
-  for (int u = 0; u < U; ++u) {
-    const int64_t row = base + u * G + g;
-    const bool ok = row < n;
-    const int64_t rowc = ok ? row : n - 1;
-    yv[u] = y[rowc];
-    if (UNW) {
-      wv[u] = 1.f;
-    } else {
-      const float w0 = sw ? sw[rowc] : 1.f;
-      wv[u] = ok ? w0 : 0.f;
-    }
-#pragma unroll
-    for (int k = 0; k < CPL; ++k) {
-      const int ch = c + k * LPR;
-      const int chc = ch < nch ? ch : nch - 1;
-      float4_ lo, hi;
-      load_chunk_f32(X, ld, rowc, chc, lo, hi);
-      xv[u][k][0] = ch < nch ? lo : float4_{0.f, 0.f, 0.f, 0.f};
-      xv[u][k][1] = ch < nch ? hi : float4_{0.f, 0.f, 0.f, 0.f};
-    }
-  }
-#pragma unroll
-  for (int u = 0; u < U; ++u) {
-    const float2_ w2 = {wv[u], wv[u]};
-    const float wy = wv[u] * yv[u];
-    const float2_ wy2 = {wy, wy};
-#pragma unroll
-    for (int k = 0; k < CPL; ++k)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float2_ xx = {xv[u][k][j / 2][2 * (j % 2)], xv[u][k][j / 2][2 * (j % 2) + 1]};
-        const float2_ wx = UNW ? xx : w2 * xx;
-        s1[k][j] += wx;
-        s2[k][j] = __builtin_elementwise_fma(wx, xx, s2[k][j]);
-        syx[k][j] = __builtin_elementwise_fma(wy2, xx, syx[k][j]);
-      }
-    if (c == 0) {
-      rsum[0] += wv[u];
-      rsum[1] += wy;
-      rsum[2] = fmaf(wy, yv[u], rsum[2]);
-    }
-  }
-}
-
+// Summarizer + first-gradient pass (glm_stats_mixed_kernel, resident role), U rows per lane.
 template <int LPR, int CPL, int U, int MW>
 __global__ __launch_bounds__(kBlock, MW) void glm_stats_f32_kernel(
     const float* __restrict__ X, int64_t ld, int64_t n, const float* __restrict__ y, const float* __restrict__ sw,
     float* __restrict__ partial, int pstride) {
-  constexpr int G = kWave / LPR;
-  constexpr int RT = G * U;
-  constexpr int DP = LPR * CPL * 8;
+  constexpr int RT = kWave / LPR * U;
   const int lane = threadIdx.x & (kWave - 1);
   const int wid = threadIdx.x / kWave;
   const int g = lane / LPR, c = lane % LPR;
@@ -1873,221 +1824,33 @@ __global__ __launch_bounds__(kBlock, MW) void glm_stats_f32_kernel(
   for (int64_t t = gw; t < ntiles; t += nw) {
     const int64_t base = t * RT;
     if (sw == nullptr && base + RT <= n)
-      stats_tile_f32<LPR, CPL, U, true>(base, n, X, ld, nch, y, sw, g, c, s1, s2, syx, rsum);
+      stats_tile<RowsF32, LPR, CPL, U, true>(base, n, X, ld, nch, y, sw, 0u, 0, g, c, s1, s2, syx, rsum);
     else
-      stats_tile_f32<LPR, CPL, U, false>(base, n, X, ld, nch, y, sw, g, c, s1, s2, syx, rsum);
+      stats_tile<RowsF32, LPR, CPL, U, false>(base, n, X, ld, nch, y, sw, 0u, 0, g, c, s1, s2, syx, rsum);
   }
-  // fold the G row groups of the wave, then the waves through LDS in a fixed order
-  __shared__ float red[kWavesPerBlock][3 * DP + 4];
-#pragma unroll
-  for (int k = 0; k < CPL; ++k)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        float a = s1[k][j][h], b = s2[k][j][h], e = syx[k][j][h];
-#pragma unroll
-        for (int off = LPR; off < kWave; off <<= 1) {
-          a += __shfl_xor(a, off, kWave);
-          b += __shfl_xor(b, off, kWave);
-          e += __shfl_xor(e, off, kWave);
-        }
-        const int col = 8 * (c + k * LPR) + 2 * j + h;
-        if (lane < LPR) {
-          red[wid][col] = a;
-          red[wid][DP + col] = b;
-          red[wid][2 * DP + col] = e;
-        }
-      }
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    const float v = wave_sum(rsum[q]);
-    if (lane == 0) red[wid][3 * DP + q] = v;
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < 3 * DP + 3; i += kBlock) {
-    float s = 0.f;
-#pragma unroll
-    for (int q = 0; q < kWavesPerBlock; ++q) s += red[q][i];
-    partial[(int64_t)blockIdx.x * pstride + i] = s;
-  }
+  stats_epilogue<LPR, CPL>(s1, s2, syx, rsum, partial, pstride, lane, wid, c);
 }
 
-// margins[i] = x_i . coef + intercept over fp32 rows (glm_margin_kernel).
 template <int LPR, int CPL>
 __global__ __launch_bounds__(kBlock) void glm_margin_f32_kernel(
     const float* __restrict__ X, int64_t ld, int64_t n, const float* __restrict__ coef, float intercept,
     float* __restrict__ out) {
-  constexpr int G = kWave / LPR;
-  constexpr int UNROLL = CPL >= 4 ? 1 : 4 / CPL;
-  const int lane = threadIdx.x & (kWave - 1);
-  const int g = lane / LPR, c = lane % LPR;
-  const int nch = (int)(ld / 8);
-  float w[CPL][8];
-#pragma unroll
-  for (int k = 0; k < CPL; ++k)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int col = 8 * (c + k * LPR) + j;
-      w[k][j] = col < ld ? coef[col] : 0.f;
-    }
-  const int64_t gw = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
-  const int64_t nw = ((int64_t)gridDim.x * blockDim.x) / kWave;
-  const int64_t RT = (int64_t)G * UNROLL;
-  const int64_t ntiles = (n + RT - 1) / RT;
-  for (int64_t t = gw; t < ntiles; t += nw) {
-    float4_ xv[UNROLL][CPL][2];
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) {
-      const int64_t row = t * RT + u * G + g;
-      const int64_t rowc = row < n ? row : n - 1;
-#pragma unroll
-      for (int k = 0; k < CPL; ++k) {
-        const int ch = c + k * LPR;
-        const int chc = ch < nch ? ch : nch - 1;
-        float4_ lo, hi;
-        load_chunk_f32(X, ld, rowc, chc, lo, hi);
-        xv[u][k][0] = ch < nch ? lo : float4_{0.f, 0.f, 0.f, 0.f};
-        xv[u][k][1] = ch < nch ? hi : float4_{0.f, 0.f, 0.f, 0.f};
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) {
-      const int64_t row = t * RT + u * G + g;
-      float d = 0.f;
-#pragma unroll
-      for (int k = 0; k < CPL; ++k)
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) d = fmaf(xv[u][k][h][j], w[k][4 * h + j], d);
-      d = group_sum<LPR>(d);
-      if (row < n && c == 0) out[row] = d + intercept;
-    }
-  }
+  margin_body<RowsF32, LPR, CPL, (CPL >= 4 ? 1 : 4 / CPL)>(X, ld, n, coef, intercept, out);
 }
 
-// Weighted column moments over fp32 rows (glm_colstats_kernel, SRC == 0).
 template <int LPR, int CPL>
 __global__ __launch_bounds__(kBlock) void glm_colstats_f32_kernel(
     const float* __restrict__ X, int64_t ld, int64_t n, const float* __restrict__ sw, float* __restrict__ partial,
     int pstride) {
-  constexpr int G = kWave / LPR;
-  constexpr int UNROLL = CPL >= 4 ? 1 : 4 / CPL;
-  constexpr int DP = LPR * CPL * 8;
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wid = threadIdx.x / kWave;
-  const int g = lane / LPR, c = lane % LPR;
-  const int nch = (int)(ld / 8);
-  float s1[CPL][8], s2[CPL][8];
-#pragma unroll
-  for (int k = 0; k < CPL; ++k)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) s1[k][j] = s2[k][j] = 0.f;
-  float sw_acc = 0.f;
-  const int64_t RT = (int64_t)G * UNROLL;
-  const int64_t ntiles = (n + RT - 1) / RT;
-  const int64_t gw = (int64_t)blockIdx.x * kWavesPerBlock + wid;
-  const int64_t nw = (int64_t)gridDim.x * kWavesPerBlock;
-  for (int64_t t = gw; t < ntiles; t += nw) {
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) {
-      const int64_t row = t * RT + u * G + g;
-      const bool ok = row < n;
-      const int64_t rowc = ok ? row : n - 1;
-      const float wv = sw ? sw[rowc] : 1.f;
-      const float w = ok ? wv : 0.f;
-#pragma unroll
-      for (int k = 0; k < CPL; ++k) {
-        const int ch = c + k * LPR;
-        const int chc = ch < nch ? ch : nch - 1;
-        float4_ xq[2];
-        load_chunk_f32(X, ld, rowc, chc, xq[0], xq[1]);
-        const float wk = ch < nch ? w : 0.f;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const float x = xq[j / 4][j % 4];
-          const float wx = wk * x;
-          s1[k][j] += wx;
-          s2[k][j] = fmaf(wx, x, s2[k][j]);
-        }
-      }
-      if (c == 0) sw_acc += w;
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < CPL; ++k)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float a = s1[k][j], b = s2[k][j];
-#pragma unroll
-      for (int off = LPR; off < kWave; off <<= 1) {
-        a += __shfl_xor(a, off, kWave);
-        b += __shfl_xor(b, off, kWave);
-      }
-      s1[k][j] = a;
-      s2[k][j] = b;
-    }
-  sw_acc = wave_sum(sw_acc);
-  // waves add into one LDS row in turn (fixed order -> deterministic)
-  __shared__ float red[2 * DP + 2];
-  for (int q = 0; q < kWavesPerBlock; ++q) {
-    if (wid == q) {
-      if (lane < LPR) {
-#pragma unroll
-        for (int k = 0; k < CPL; ++k)
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            const int i1 = 8 * (c + k * LPR) + j;
-            red[i1] = (q == 0 ? 0.f : red[i1]) + s1[k][j];
-            red[DP + i1] = (q == 0 ? 0.f : red[DP + i1]) + s2[k][j];
-          }
-      }
-      if (lane == 0) red[2 * DP] = (q == 0 ? 0.f : red[2 * DP]) + sw_acc;
-    }
-    __syncthreads();
-  }
-  for (int i = threadIdx.x; i < 2 * DP + 1; i += kBlock) partial[(int64_t)blockIdx.x * pstride + i] = red[i];
+  colstats_body<RowsF32, LPR, CPL>(X, ld, n, sw, 0u, 0, partial, pstride);
 }
 
-// Rows in flight per lane (UNROLL) and waves per SIMD asked of the register allocator (MW)
-// of the fp32 gradient pass, per chunks-per-lane: the widest layouts keep one row at a time
+// Rows in flight per lane (U) and waves per SIMD asked of the register allocator (MW) of
+// the fp32 gradient pass, per chunks-per-lane: the widest layouts keep one row at a time
 // and one wave per SIMD so that w + acc + the row stay in registers.
 template <int C> struct F32Cfg { static constexpr int U = C >= 8 ? 1 : 8 / C, MW = C >= 8 ? 1 : 2; };
 
-template <int L, int C, bool SMP>
-void launch_grad_f32(int loss, int grid, hipStream_t st, const float* X, int64_t ld, int64_t n, const float* y,
-                     const float* sw, const float* coef, const float* b, float* partial, int pstride,
-                     int64_t res_row0, const int64_t* t_dev, uint32_t sseed, uint32_t sthr, int pacc) {
-  constexpr int U = F32Cfg<C>::U, MW = F32Cfg<C>::MW;
-  if (loss == LOSS_LOGISTIC)
-    hipLaunchKernelGGL((glm_grad_f32_kernel<L, C, U, LOSS_LOGISTIC, MW, SMP>), dim3(grid), dim3(kBlock), 0, st, X, ld,
-                       n, y, sw, coef, b, partial, pstride, res_row0, t_dev, sseed, sthr, pacc);
-  else if (loss == LOSS_HINGE)
-    hipLaunchKernelGGL((glm_grad_f32_kernel<L, C, U, LOSS_HINGE, MW, SMP>), dim3(grid), dim3(kBlock), 0, st, X, ld, n,
-                       y, sw, coef, b, partial, pstride, res_row0, t_dev, sseed, sthr, pacc);
-  else
-    hipLaunchKernelGGL((glm_grad_f32_kernel<L, C, U, LOSS_SQUARED, MW, SMP>), dim3(grid), dim3(kBlock), 0, st, X, ld,
-                       n, y, sw, coef, b, partial, pstride, res_row0, t_dev, sseed, sthr, pacc);
-}
-
-// (lpr_s, cpl_s) of the mixed pass for row stride ld; false when ld has no layout.
-bool f32_layout(int64_t ld, int* lpr_s, int* cpl_s, int* dpad) {
-  const int nch = (int)(ld / 8);
-  const int lpr = pick_lpr(nch), cpl = pick_cpl(nch);
-  if (ld <= 0 || ld % 8 != 0 || cpl > 16) return false;
-  *lpr_s = lpr;
-  *cpl_s = cpl;
-  if (cpl == 1 && lpr >= 16) { *lpr_s = lpr / 4; *cpl_s = 4; }
-  else if (cpl == 2) { *lpr_s = 32; *cpl_s = 4; }
-  *dpad = lpr * cpl * 8;
-  return true;
-}
-
 }  // namespace
-
-// Every layout of the fp32 passes (the mixed pass's list).
-#define O3S_F32_LAYOUTS(M) M(4, 1) M(8, 1) M(4, 4) M(8, 4) M(16, 4) M(32, 4) M(64, 4) M(64, 8) M(64, 16)
 
 // Gradient/loss pass over fp32 rows: the out / coef / partial contract of o3s_glm_grad
 // (accumulate adds into out) with the mini-batch sampler and the splits loop of
@@ -2096,115 +1859,79 @@ O3S_API int o3s_glm_grad_f32(int loss, const void* X, int64_t ld, int64_t n, con
                              const float* coef, int64_t n_lin, float* partial, int grid, double* out,
                              int accumulate, int64_t res_row0, const int64_t* t_dev, uint32_t sseed, uint32_t sthr,
                              int splits, hipStream_t st) {
-  int lpr_s, cpl_s, dpad;
-  if (!f32_layout(ld, &lpr_s, &cpl_s, &dpad) || grid <= 0 || n < 0 || n_lin != 0) return -1;
-  const int pstride = dpad + 4;
+  Layout l;
+  if (ld <= 0 || !resolve_layout(ld, &l) || grid <= 0 || n < 0 || n_lin != 0) return -1;
+  const int pstride = l.dpad + 4;
   const float* Xf = (const float*)X;
-  const float* b = coef + dpad;
   const bool smp = sthr < (1u << 24);
-#define O3S_GF(L, C)                                                                                         \
-  if (!done && lpr_s == L && cpl_s == C) {                                                                   \
-    done = true;                                                                                             \
-    if (smp)                                                                                                 \
-      launch_grad_f32<L, C, true>(loss, grid, st, XS, ld, NR, YR, SWR, coef, b, partial, pstride, RR0, t_dev, \
-                                  sseed, sthr, k > 0);                                                       \
-    else                                                                                                     \
-      launch_grad_f32<L, C, false>(loss, grid, st, XS, ld, NR, YR, SWR, coef, b, partial, pstride, RR0, t_dev, \
-                                   sseed, sthr, k > 0);                                                      \
-  }
-  const int K = splits < 1 ? 1 : splits;
-  for (int k = 0; k < K; ++k) {
-    const int64_t r_lo = n * k / K, r_hi = n * (k + 1) / K;
-    const float* XS = Xf + r_lo * ld;
-    const int64_t NR = r_hi - r_lo, RR0 = res_row0 + r_lo;
-    const float* YR = y + r_lo;
-    const float* SWR = sw ? sw + r_lo : nullptr;
-    bool done = false;
-    O3S_F32_LAYOUTS(O3S_GF)
-    if (!done) return -1;
-    O3S_CHECK_LAUNCH();
-  }
-#undef O3S_GF
-  const int ncols = dpad + 3;
-  hipLaunchKernelGGL(glm_finish_kernel, dim3((ncols + 31) / 32), dim3(1024), 0, st, partial, grid, pstride, ncols,
-                     out, accumulate);
-  O3S_CHECK_LAUNCH();
-  return 0;
+  const int rc = for_row_slices(splits, n, 0, [&](int64_t r_lo, int64_t r_n, int64_t, int64_t, int pacc) {
+    return with_remapped_layout_and_loss(l, loss, [&](auto L, auto C, auto LOSS) {
+      constexpr int U = F32Cfg<C>::U, MW = F32Cfg<C>::MW;
+      auto go = [&](auto SMP) {
+        launch(glm_grad_f32_kernel<L, C, U, LOSS, MW, SMP>, grid, st, Xf + r_lo * ld, ld, r_n, y + r_lo,
+               sw ? sw + r_lo : nullptr, coef, coef + l.dpad, partial, pstride, res_row0 + r_lo, t_dev, sseed, sthr,
+               pacc);
+      };
+      if (smp) go(std::true_type{});
+      else go(std::false_type{});
+      return 0;
+    });
+  });
+  if (rc != 0) return rc;
+  return launch_finish(partial, grid, pstride, l.dpad + 3, out, accumulate, st);
 }
 
 // Fused summarizer + first-gradient pass over fp32 rows: the out / partial contract of
 // o3s_glm_stats_mixed, -2 for the layouts that one has no instantiation for (ld > 2048).
 O3S_API int o3s_glm_stats_f32(const void* X, int64_t ld, int64_t n, const float* y, const float* sw, int64_t n_lin,
                               float* partial, int grid, double* out, hipStream_t st) {
-  int lpr_s, cpl_s, dpad;
-  if (!f32_layout(ld, &lpr_s, &cpl_s, &dpad) || grid <= 0 || n < 0 || n_lin != 0) return -1;
-  const int pstride = 3 * dpad + 4;
-  const float* Xf = (const float*)X;
-  bool done = false;
-#define O3S_SF(L, C)                                                                                        \
-  if (!done && lpr_s == L && cpl_s == C) {                                                                  \
-    done = true;                                                                                            \
-    hipLaunchKernelGGL((glm_stats_f32_kernel<L, C, (C >= 4 ? 1 : 4 / C), 2>), dim3(grid), dim3(kBlock), 0, st, Xf, \
-                       ld, n, y, sw, partial, pstride);                                                     \
-  }
-  O3S_SF(4, 1) O3S_SF(8, 1) O3S_SF(4, 4) O3S_SF(8, 4) O3S_SF(16, 4) O3S_SF(32, 4) O3S_SF(64, 4)
-#undef O3S_SF
-  if (!done) return -2;
-  O3S_CHECK_LAUNCH();
-  const int ncols = 3 * dpad + 3;
-  hipLaunchKernelGGL(glm_finish_kernel, dim3((ncols + 31) / 32), dim3(1024), 0, st, partial, grid, pstride, ncols,
-                     out, 0);
-  O3S_CHECK_LAUNCH();
-  return 0;
+  Layout l;
+  if (ld <= 0 || !resolve_layout(ld, &l) || grid <= 0 || n < 0 || n_lin != 0) return -1;
+  const int pstride = 3 * l.dpad + 4;
+  const int rc = with_remapped_layout(l, [&](auto L, auto C) {
+    if constexpr (C > 4) {
+      return -2;
+    } else {
+      launch(glm_stats_f32_kernel<L, C, (C >= 4 ? 1 : 4 / C), 2>, grid, st, (const float*)X, ld, n, y, sw, partial,
+             pstride);
+      return 0;
+    }
+  });
+  if (rc != 0) return rc;
+  return launch_finish(partial, grid, pstride, 3 * l.dpad + 3, out, 0, st);
 }
 
 O3S_API int o3s_glm_margin_f32(const void* X, int64_t ld, int64_t n, const float* coef, float intercept, float* out,
                                int grid, hipStream_t st) {
-  int lpr_s, cpl_s, dpad;
-  if (!f32_layout(ld, &lpr_s, &cpl_s, &dpad) || grid <= 0) return -1;
+  Layout l;
+  if (ld <= 0 || !resolve_layout(ld, &l) || grid <= 0) return -1;
   if (n <= 0) return 0;
-  const float* Xf = (const float*)X;
-#define O3S_MF(L, C)                                                                                          \
-  if (lpr_s == L && cpl_s == C) {                                                                             \
-    hipLaunchKernelGGL((glm_margin_f32_kernel<L, C>), dim3(grid), dim3(kBlock), 0, st, Xf, ld, n, coef,       \
-                       intercept, out);                                                                       \
-    O3S_CHECK_LAUNCH();                                                                                       \
-    return 0;                                                                                                 \
-  }
-  O3S_F32_LAYOUTS(O3S_MF)
-#undef O3S_MF
-  return -1;
+  return with_remapped_layout(l, [&](auto L, auto C) {
+    launch(glm_margin_f32_kernel<L, C>, grid, st, (const float*)X, ld, n, coef,
+           intercept, out);
+    O3S_CHECK_LAUNCH();
+    return 0;
+  });
 }
 
 // Column moments over fp32 rows: the out / partial contract of o3s_glm_colstats.
 O3S_API int o3s_glm_colstats_f32(const void* X, int64_t ld, int64_t n, const float* sw, float* partial, int grid,
                                  double* out, hipStream_t st) {
-  int lpr_s, cpl_s, dpad;
-  if (!f32_layout(ld, &lpr_s, &cpl_s, &dpad) || grid <= 0 || n < 0) return -1;
-  const int pstride = 2 * dpad + 2;
-  const float* Xf = (const float*)X;
+  Layout l;
+  if (ld <= 0 || !resolve_layout(ld, &l) || grid <= 0 || n < 0) return -1;
+  const int pstride = 2 * l.dpad + 2;
   if (n > 0) {
-    bool done = false;
-#define O3S_CF(L, C)                                                                                          \
-  if (!done && lpr_s == L && cpl_s == C) {                                                                    \
-    hipLaunchKernelGGL((glm_colstats_f32_kernel<L, C>), dim3(grid), dim3(kBlock), 0, st, Xf, ld, n, sw,       \
-                       partial, pstride);                                                                     \
-    done = true;                                                                                              \
-  }
-    O3S_F32_LAYOUTS(O3S_CF)
-#undef O3S_CF
-    if (!done) return -1;
+    const int rc = with_remapped_layout(l, [&](auto L, auto C) {
+      launch(glm_colstats_f32_kernel<L, C>, grid, st, (const float*)X, ld, n, sw,
+             partial, pstride);
+      return 0;
+    });
+    if (rc != 0) return rc;
   } else {
     hipMemsetAsync(partial, 0, sizeof(float) * pstride * (size_t)grid, st);
   }
-  O3S_CHECK_LAUNCH();
-  const int ncols = 2 * dpad + 1;
-  hipLaunchKernelGGL(glm_finish_kernel, dim3((ncols + 31) / 32), dim3(1024), 0, st, partial, grid, pstride, ncols,
-                     out, 0);
-  O3S_CHECK_LAUNCH();
-  return 0;
+  return launch_finish(partial, grid, pstride, 2 * l.dpad + 1, out, 0, st);
 }
-#undef O3S_F32_LAYOUTS
 
 // ---------------------------------------------------------------------------------
 // Multinomial pass over fp32 rows: the contract, MFMA layouts, slab rows and finish of

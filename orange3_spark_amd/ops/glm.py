@@ -419,26 +419,18 @@ def _coef_buf(coef: torch.Tensor, dpad: int, device, slot: int = 0,
 def glm_margin(X: torch.Tensor, coef: torch.Tensor, intercept: float) -> torch.Tensor:
     """margins = X . coef + intercept (fp32 [n])."""
     ld = X.shape[1]
-    if X.is_cuda and X.dtype == torch.bfloat16 and X.is_contiguous():
+    if kernel_rows(X):
         dpad, _ = layout(ld)
         cf = torch.zeros(dpad, dtype=torch.float32, device=X.device)
         k = min(coef.shape[0], dpad)
         cf[:k] = coef[:k].to(X.device, torch.float32)
         out = torch.empty(X.shape[0], dtype=torch.float32, device=X.device)
         lib = N.kernels()
+        fn, what = ((lib.o3s_glm_margin_f32, "glm_margin_f32") if X.dtype == torch.float32
+                    else (lib.o3s_glm_margin, "glm_margin"))
         grid = N.grid_for(X.device, X.shape[0], 64)
-        N.check(lib.o3s_glm_margin(X.data_ptr(), ld, X.shape[0], cf.data_ptr(), float(intercept),
-                                   out.data_ptr(), grid, N.stream_of(X)), "glm_margin")
-        return out
-    if f32_rows(X):
-        dpad, _ = layout(ld)
-        cf = torch.zeros(dpad, dtype=torch.float32, device=X.device)
-        k = min(coef.shape[0], dpad)
-        cf[:k] = coef[:k].to(X.device, torch.float32)
-        out = torch.empty(X.shape[0], dtype=torch.float32, device=X.device)
-        grid = N.grid_for(X.device, X.shape[0], 64)
-        N.check(N.kernels().o3s_glm_margin_f32(X.data_ptr(), ld, X.shape[0], cf.data_ptr(), float(intercept),
-                                               out.data_ptr(), grid, N.stream_of(X)), "glm_margin_f32")
+        N.check(fn(X.data_ptr(), ld, X.shape[0], cf.data_ptr(), float(intercept), out.data_ptr(), grid,
+                   N.stream_of(X)), what)
         return out
     c = coef.to(X.device, torch.float64)[:ld]
     return (X.to(torch.float64) @ c + float(intercept)).to(torch.float32)
@@ -511,18 +503,16 @@ def _colstats_out(ld: int, device, grid: int):
 def glm_colstats(X: torch.Tensor, sw: torch.Tensor | None = None) -> torch.Tensor:
     """fp64 [sum w x (ld) | sum w x^2 (ld) | sum w] over the rows of X."""
     ld = X.shape[1]
-    if X.is_cuda and X.dtype == torch.bfloat16 and X.is_contiguous():
+    if kernel_rows(X):
         grid = N.num_cus(X.device) * 4
         dpad, partial, out = _colstats_out(ld, X.device, grid)
-        N.check(N.kernels().o3s_glm_colstats(0, X.data_ptr(), ld, X.shape[0], N.ptr(sw), 0, 0,
-                                             partial.data_ptr(), grid, out.data_ptr(), N.stream_of(X)),
-                "glm_colstats")
-        return torch.cat([out[:ld], out[dpad:dpad + ld], out[2 * dpad:]])
-    if f32_rows(X):
-        grid = N.num_cus(X.device) * 4
-        dpad, partial, out = _colstats_out(ld, X.device, grid)
-        N.check(N.kernels().o3s_glm_colstats_f32(X.data_ptr(), ld, X.shape[0], N.ptr(sw), partial.data_ptr(), grid,
-                                                 out.data_ptr(), N.stream_of(X)), "glm_colstats_f32")
+        lib = N.kernels()
+        if X.dtype == torch.float32:
+            N.check(lib.o3s_glm_colstats_f32(X.data_ptr(), ld, X.shape[0], N.ptr(sw), partial.data_ptr(), grid,
+                                             out.data_ptr(), N.stream_of(X)), "glm_colstats_f32")
+        else:
+            N.check(lib.o3s_glm_colstats(0, X.data_ptr(), ld, X.shape[0], N.ptr(sw), 0, 0, partial.data_ptr(), grid,
+                                         out.data_ptr(), N.stream_of(X)), "glm_colstats")
         return torch.cat([out[:ld], out[dpad:dpad + ld], out[2 * dpad:]])
     Xd = X.to(torch.float64)
     w = torch.ones(X.shape[0], dtype=torch.float64, device=X.device) if sw is None else sw.to(torch.float64)
