@@ -563,7 +563,9 @@ __host__ __device__ __forceinline__ uint32_t sample_key(uint32_t seed, uint32_t 
 
 // One gradient tile of RT = G * UNROLL rows from source SRC.  Labels / weights come from
 // the materialised label column (y, sw already offset to the role's first row).
-template <class SRC, int LPR, int CPL, int UNROLL, int LOSS, bool SMP>
+// FULL: every row of the tile is < n and every chunk of the layout is < nch (the caller
+// guarantees both), so rows, chunks and labels are read unclamped and nothing is masked.
+template <class SRC, int LPR, int CPL, int UNROLL, int LOSS, bool SMP, bool FULL = false>
 __device__ __forceinline__ void grad_tile(
     int64_t base, int64_t n, const typename SRC::elem* __restrict__ X, int64_t ld, int nch,
     const float* __restrict__ y, const float* __restrict__ sw, uint32_t seed, int64_t row0, const float (&w)[CPL][8],
@@ -586,6 +588,8 @@ __device__ __forceinline__ void grad_tile(
       const int ch = c + k * LPR;
       if constexpr (SRC::kLineage) {
         SRC::decode(synth_word(fk, 2 * ch), synth_word(fk, 2 * ch + 1), xv[u][k]);
+      } else if constexpr (FULL) {
+        SRC::load(X, ld, row, ch, xv[u][k]);
       } else {
         const int chc = ch < nch ? ch : nch - 1;
         SRC::load(X, ld, rowc, chc, xv[u][k]);
@@ -600,10 +604,15 @@ __device__ __forceinline__ void grad_tile(
     const int64_t row = base + (ubase + j) * G + g;
     const bool ok = row < n;
     const int64_t rowc = ok ? row : n - 1;
-    const float yv = y[rowc];
-    const float wv = sw ? sw[rowc] : 1.f;
-    yy[j] = ok ? yv : 0.f;
-    ww[j] = ok ? wv : 0.f;
+    if constexpr (FULL) {
+      yy[j] = y[row];
+      ww[j] = sw ? sw[row] : 1.f;
+    } else {
+      const float yv = y[rowc];
+      const float wv = sw ? sw[rowc] : 1.f;
+      yy[j] = ok ? yv : 0.f;
+      ww[j] = ok ? wv : 0.f;
+    }
     if constexpr (SMP) {
       if (!smp.keep(row)) ww[j] = 0.f;
     }
@@ -664,7 +673,10 @@ __device__ __forceinline__ void grad_tile(
 // D = 256, 174 VGPRs; 3 = 168 VGPRs with a 4-register spill outside the tile loop).
 // Every wave walks the interleaved tile sequence (both roles per wave; fixed-role layouts
 // -- some waves regenerating, the others streaming -- measured slower and were removed).
-template <int LPR, int CPL, int UNROLL, int LOSS, int MW, bool SMP>
+// FULL: n_res and n_lin are multiples of RT and ld is the layout's full width, so both tile
+// bodies drop their clamps and masks (grad_tile); the host launches the ragged rest apart
+// (o3s_glm_grad_mixed).  The loop holds two tile bodies either way: a third one spills.
+template <int LPR, int CPL, int UNROLL, int LOSS, int MW, bool SMP, bool FULL = false>
 __global__ __launch_bounds__(kBlock, MW) void glm_grad_mixed_kernel(
     const uint16_t* __restrict__ X, int64_t ld, int64_t n_res, const float* __restrict__ y,
     const float* __restrict__ sw, const float* __restrict__ y_lin, const float* __restrict__ sw_lin,
@@ -710,11 +722,12 @@ __global__ __launch_bounds__(kBlock, MW) void glm_grad_mixed_kernel(
     const int64_t q0 = nw * Tl / S, r0 = nw * Tl - q0 * S;
     for (int64_t s = gw; s < S; s += nw) {
       if (rem + Tl >= S)
-        grad_tile<RowsLineage, LPR, CPL, UNROLL, LOSS, SMP>(L * RT, n_lin, X, ld, nch, y_lin, sw_lin, seed, row0, w, wshift,
-                                                            intercept, g, c, smp_lin, acc, rs, acc_r, acc_loss, acc_w);
+        grad_tile<RowsLineage, LPR, CPL, UNROLL, LOSS, SMP, FULL>(L * RT, n_lin, X, ld, nch, y_lin, sw_lin, seed, row0, w,
+                                                                  wshift, intercept, g, c, smp_lin, acc, rs, acc_r, acc_loss,
+                                                                  acc_w);
       else
-        grad_tile<RowsBf16, LPR, CPL, UNROLL, LOSS, SMP>((s - L) * RT, n_res, X, ld, nch, y, sw, seed, row0, w, wshift, intercept,
-                                                         g, c, smp_res, acc, rs, acc_r, acc_loss, acc_w);
+        grad_tile<RowsBf16, LPR, CPL, UNROLL, LOSS, SMP, FULL>((s - L) * RT, n_res, X, ld, nch, y, sw, seed, row0, w, wshift,
+                                                               intercept, g, c, smp_res, acc, rs, acc_r, acc_loss, acc_w);
       rem += r0;
       L += q0;
       if (rem >= S) { rem -= S; ++L; }
@@ -739,7 +752,9 @@ __global__ __launch_bounds__(kBlock, MW) void glm_grad_mixed_kernel(
 // and regenerate each chunk where it is used.
 // UNW: a full tile (every row < n) of an unweighted fit -- w = 1 is folded away, which
 // drops the w*x product from every element (the pass is VALU-bound on lineage tiles).
-template <class SRC, int LPR, int CPL, int U, bool UNW>
+// FULL: every row of the tile is < n and every chunk of the layout is < nch: no clamps, no
+// masks; a weighted FULL tile (UNW false) has a weight column (sw is not null).
+template <class SRC, int LPR, int CPL, int U, bool UNW, bool FULL = false>
 __device__ __forceinline__ void stats_tile(int64_t base, int64_t n, const typename SRC::elem* __restrict__ X,
                                            int64_t ld, int nch, const float* __restrict__ y,
                                            const float* __restrict__ sw, uint32_t seed, int64_t row0, int g, int c,
@@ -753,10 +768,12 @@ __device__ __forceinline__ void stats_tile(int64_t base, int64_t n, const typena
   for (int u = 0; u < U; ++u) {
     const int64_t row = base + u * G + g;
     const bool ok = row < n;
-    const int64_t rowc = ok ? row : n - 1;
+    const int64_t rowc = FULL ? row : (ok ? row : n - 1);
     yv[u] = y[rowc];
     if (UNW) {
       wv[u] = 1.f;
+    } else if constexpr (FULL) {
+      wv[u] = sw[row];
     } else {
       const float w0 = sw ? sw[rowc] : 1.f;
       wv[u] = ok ? w0 : 0.f;
@@ -767,8 +784,12 @@ __device__ __forceinline__ void stats_tile(int64_t base, int64_t n, const typena
 #pragma unroll
       for (int k = 0; k < CPL; ++k) {
         const int ch = c + k * LPR;
-        SRC::load(X, ld, rowc, ch < nch ? ch : nch - 1, xv[u][k]);
-        SRC::mask(xv[u][k], ch < nch);
+        if constexpr (FULL) {
+          SRC::load(X, ld, row, ch, xv[u][k]);
+        } else {
+          SRC::load(X, ld, rowc, ch < nch ? ch : nch - 1, xv[u][k]);
+          SRC::mask(xv[u][k], ch < nch);
+        }
       }
     }
   }
@@ -844,11 +865,14 @@ __device__ __forceinline__ void stats_epilogue(const float2_ (&s1)[CPL][4], cons
   }
 }
 
-template <int LPR, int CPL, int MW>
+// FULL: 0 = any row counts (four tile bodies in the loop); 1 / 2 = n_res and n_lin are
+// multiples of RT and ld is the layout's full width, an unweighted (1) or a weighted (2) pass:
+// the loop holds that one pair of mask-free bodies.  y_lin / sw_lin: the lineage rows' labels.
+template <int LPR, int CPL, int MW, int FULL = 0>
 __global__ __launch_bounds__(kBlock, MW) void glm_stats_mixed_kernel(
     const uint16_t* __restrict__ X, int64_t ld, int64_t n_res, const float* __restrict__ y,
-    const float* __restrict__ sw, uint32_t seed, int64_t row0, int64_t n_lin, float* __restrict__ partial,
-    int pstride) {
+    const float* __restrict__ sw, const float* __restrict__ y_lin, const float* __restrict__ sw_lin, uint32_t seed,
+    int64_t row0, int64_t n_lin, float* __restrict__ partial, int pstride) {
   constexpr int G = kWave / LPR;
   constexpr int U = CPL >= 8 ? 1 : 8 / CPL;
   constexpr int RT = G * U;
@@ -856,8 +880,6 @@ __global__ __launch_bounds__(kBlock, MW) void glm_stats_mixed_kernel(
   const int wid = threadIdx.x / kWave;
   const int g = lane / LPR, c = lane % LPR;
   const int nch = (int)(ld / 8);
-  const float* y_lin = y + n_res;
-  const float* sw_lin = sw ? sw + n_res : nullptr;
   float2_ s1[CPL][4], s2[CPL][4], syx[CPL][4];
 #pragma unroll
   for (int k = 0; k < CPL; ++k)
@@ -874,7 +896,14 @@ __global__ __launch_bounds__(kBlock, MW) void glm_stats_mixed_kernel(
       // full tiles of an unweighted pass take the UNW body (chosen here and in
       // glm_stats_f32_kernel, and s1 / s2 / syx zeroed by a plain loop in both: either one in a
       // helper took glm_stats_mixed_kernel<8,4,2> from 184 to 256 VGPRs)
-      if (rem + Tl >= S) {
+      if constexpr (FULL != 0) {
+        if (rem + Tl >= S)
+          stats_tile<RowsLineage, LPR, CPL, U, FULL == 1, true>(L * RT, n_lin, X, ld, nch, y_lin, sw_lin, seed, row0, g, c,
+                                                               s1, s2, syx, rsum);
+        else
+          stats_tile<RowsBf16, LPR, CPL, U, FULL == 1, true>((s - L) * RT, n_res, X, ld, nch, y, sw, seed, row0, g, c, s1,
+                                                            s2, syx, rsum);
+      } else if (rem + Tl >= S) {
         const int64_t base = L * RT;
         if (sw == nullptr && base + RT <= n_lin)
           stats_tile<RowsLineage, LPR, CPL, U, true>(base, n_lin, X, ld, nch, y_lin, sw_lin, seed, row0, g, c, s1,
@@ -1258,12 +1287,15 @@ int launch_finish(const float* partial, int grid, int pstride, int ncols, double
 // apart, so the resident stream touches a wider address window; restarting the walk every
 // 1/splits of a 255 GB table measured 44.2 -> 43.7 ms even with a finish per slice
 // (tools/bench_glm_split_ab.py).  slice(r_lo, r_n, l_lo, l_n, pacc) launches one slice.
+// unit: every slice boundary, the last included, is rounded down to a multiple of it, so
+// the slices cover the whole tiles of each role and leave fewer than `unit` rows of each.
 template <class F>
-int for_row_slices(int splits, int64_t n_res, int64_t n_lin, F&& slice) {
+int for_row_slices(int splits, int64_t n_res, int64_t n_lin, F&& slice, int64_t unit = 1) {
   const int K = splits < 1 ? 1 : splits;
+  const auto cut = [&](int64_t n, int k) { return n * k / K / unit * unit; };
   for (int k = 0; k < K; ++k) {
-    const int64_t r_lo = n_res * k / K, l_lo = n_lin * k / K;
-    const int rc = slice(r_lo, n_res * (k + 1) / K - r_lo, l_lo, n_lin * (k + 1) / K - l_lo, k > 0);
+    const int64_t r_lo = cut(n_res, k), l_lo = cut(n_lin, k);
+    const int rc = slice(r_lo, cut(n_res, k + 1) - r_lo, l_lo, cut(n_lin, k + 1) - l_lo, k > 0);
     if (rc != 0) return rc;
     O3S_CHECK_LAUNCH();
   }
@@ -1327,24 +1359,31 @@ O3S_API int o3s_glm_grad(int loss, int src, const void* X, int64_t ld, int64_t n
 // index of resident row 0, t_dev (may be null = iteration 1) the device step counter,
 // sthr = fraction * 2^24 (>= 2^24: no sampling), sseed the sampling seed.  splits: see
 // for_row_slices.
+// full_tiles: where ld is the layout's full width, the slices are cut at whole tiles and
+// run through the mask-free kernel, and the fewer than RT rows that remain of each role go
+// through the masked kernel in one more launch of one block, which adds into slab row 0
+// (pacc; every other slab row stays as the slices left it).  0: masked kernel throughout.
 O3S_API int o3s_glm_grad_mixed(int loss, const void* X, int64_t ld, int64_t n_res, const float* y,
                                const float* sw, const float* coef, uint32_t seed, int64_t row0,
                                int64_t n_lin, float* partial, int grid, double* out, int waves,
                                int64_t res_row0, const int64_t* t_dev, uint32_t sseed,
-                               uint32_t sthr, int splits, hipStream_t st) {
+                               uint32_t sthr, int splits, int full_tiles, hipStream_t st) {
   Layout l;
   if (!resolve_layout(ld, &l) || grid <= 0 || n_res < 0 || n_lin < 0) return -1;
   const int pstride = l.dpad + 4;
   const uint16_t* Xh = (const uint16_t*)X;
   const bool smp = sthr < (1u << 24);
-  const int rc = for_row_slices(splits, n_res, n_lin, [&](int64_t r_lo, int64_t r_n, int64_t l_lo, int64_t l_n,
-                                                           int pacc) {
-    const float* y_lin = y + n_res + l_lo;
-    const float* sw_lin = sw ? sw + n_res + l_lo : nullptr;
-    return with_remapped_layout_and_loss(l, loss, [&](auto L, auto C, auto LOSS) {
-      constexpr int U = C >= 8 ? 1 : 8 / C;
+  const int rc = with_remapped_layout_and_loss(l, loss, [&](auto L, auto C, auto LOSS) {
+    constexpr int U = C >= 8 ? 1 : 8 / C;
+    constexpr int64_t RT = (kWave / L) * U;
+    // rows [r_lo, r_lo + r_n) of X and lineage rows [l_lo, l_lo + l_n) in one launch
+    auto slice = [&](auto FULL, int g, int64_t r_lo, int64_t r_n, int64_t l_lo, int64_t l_n, int pacc) {
+      // the mask-free kernel reads whole tiles unguarded: never launch it on anything else
+      if (FULL && (r_n % RT != 0 || l_n % RT != 0 || ld != 8 * L * C)) return -1;
+      const float* y_lin = y + n_res + l_lo;
+      const float* sw_lin = sw ? sw + n_res + l_lo : nullptr;
       auto go = [&](auto MW, auto SMP) {
-        launch(glm_grad_mixed_kernel<L, C, U, LOSS, MW, SMP>, grid, st, Xh + r_lo * ld, ld, r_n, y + r_lo,
+        launch(glm_grad_mixed_kernel<L, C, U, LOSS, MW, SMP, FULL>, g, st, Xh + r_lo * ld, ld, r_n, y + r_lo,
                sw ? sw + r_lo : nullptr, y_lin, sw_lin, coef, coef + l.dpad, seed, row0 + l_lo, l_n, partial, pstride,
                res_row0 + r_lo, t_dev, sseed, sthr, pacc);
       };
@@ -1353,6 +1392,27 @@ O3S_API int o3s_glm_grad_mixed(int loss, const void* X, int64_t ld, int64_t n_re
       else if (smp) go(IC<2>{}, std::true_type{});
       else go(IC<2>{}, std::false_type{});
       return 0;
+    };
+    // (the 32x4 and 64x4 layouts have no mask-free kernel: built for 3 waves/SIMD it spills
+    // where its masked twin does not)
+    constexpr bool kHasFull = !(L >= 32 && C == 4);
+    const int64_t r_full = n_res / RT * RT, l_full = n_lin / RT * RT;
+    if constexpr (kHasFull) {
+      if (full_tiles && ld == 8 * L * C && r_full + l_full > 0) {
+        const int rc = for_row_slices(
+            splits, n_res, n_lin,
+            [&](int64_t r_lo, int64_t r_n, int64_t l_lo, int64_t l_n, int pacc) {
+              return slice(std::true_type{}, grid, r_lo, r_n, l_lo, l_n, pacc);
+            },
+            RT);
+        if (rc != 0 || (r_full == n_res && l_full == n_lin)) return rc;
+        const int rc2 = slice(std::false_type{}, 1, r_full, n_res - r_full, l_full, n_lin - l_full, 1);
+        O3S_CHECK_LAUNCH();
+        return rc2;
+      }
+    }
+    return for_row_slices(splits, n_res, n_lin, [&](int64_t r_lo, int64_t r_n, int64_t l_lo, int64_t l_n, int pacc) {
+      return slice(std::false_type{}, grid, r_lo, r_n, l_lo, l_n, pacc);
     });
   });
   if (rc != 0) return rc;
@@ -1427,29 +1487,62 @@ O3S_API int o3s_glm_sgd_update_dev(const double* out, int dpad, double* bt, doub
 }
 
 // Fused summarizer + first-gradient pass (glm_stats_mixed_kernel): out (fp64, 3*dpad+3) =
-// [s1 | s2 | syx | sum w | sum w y | sum w y^2]; partial holds grid * (3*dpad+4) floats.
+// [s1 | s2 | syx | sum w | sum w y | sum w y^2]; partial holds (grid + 1) * (3*dpad+4) floats.
 // Returns -2 when the row layout has no stats instantiation (ld > 2048): the caller then
 // uses o3s_glm_colstats plus a regular first pass.
+// full_tiles: as in o3s_glm_grad_mixed -- the whole tiles of both roles run through the
+// mask-free kernel of the unweighted or of the weighted pass (sw == nullptr decides), the
+// fewer than RT rows left of each role through one block of the masked kernel, which writes
+// slab row `grid`; the finish then sums grid + 1 rows.
 O3S_API int o3s_glm_stats_mixed(const void* X, int64_t ld, int64_t n_res, const float* y, const float* sw,
                                 uint32_t seed, int64_t row0, int64_t n_lin, float* partial, int grid, double* out,
-                                int waves, hipStream_t st) {
+                                int waves, int full_tiles, hipStream_t st) {
   Layout l;
   if (!resolve_layout(ld, &l) || grid <= 0 || n_res < 0 || n_lin < 0) return -1;
   const int pstride = 3 * l.dpad + 4;
   const uint16_t* Xh = (const uint16_t*)X;
+  int slab_rows = grid;
   const int rc = with_remapped_layout(l, [&](auto L, auto C) {
     if constexpr (C > 4) {
       return -2;
     } else {
-      if (waves == 3)
-        launch(glm_stats_mixed_kernel<L, C, 3>, grid, st, Xh, ld, n_res, y, sw, seed, row0, n_lin, partial, pstride);
-      else
-        launch(glm_stats_mixed_kernel<L, C, 2>, grid, st, Xh, ld, n_res, y, sw, seed, row0, n_lin, partial, pstride);
-      return 0;
+      constexpr int64_t RT = (kWave / L) * (8 / C);
+      // rows [r_lo, r_lo + r_n) of X and lineage rows [l_lo, l_lo + l_n), g blocks, into `slab`
+      auto pass = [&](auto FULL, int g, float* slab, int64_t r_lo, int64_t r_n, int64_t l_lo, int64_t l_n) {
+        // the mask-free kernels read whole tiles (and the weighted one sw) unguarded
+        if (FULL != 0 && (r_n % RT != 0 || l_n % RT != 0 || ld != 8 * L * C || (FULL == 2) != (sw != nullptr)))
+          return -1;
+        auto go = [&](auto MW) {
+          launch(glm_stats_mixed_kernel<L, C, MW, FULL>, g, st, Xh + r_lo * ld, ld, r_n, y + r_lo,
+                 sw ? sw + r_lo : nullptr, y + n_res + l_lo, sw ? sw + n_res + l_lo : nullptr, seed, row0 + l_lo, l_n,
+                 slab, pstride);
+        };
+        // (a mask-free kernel fits 3 waves/SIMD without a spill under either bound)
+        if constexpr (FULL == 0) {
+          if (waves == 3) go(IC<3>{});
+          else go(IC<2>{});
+        } else {
+          go(IC<2>{});
+        }
+        return 0;
+      };
+      // (64x4: one wave/SIMD either way, and the weighted mask-free kernel needs more registers)
+      if constexpr (L < 64) {
+        const int64_t r_full = n_res / RT * RT, l_full = n_lin / RT * RT;
+        if (full_tiles && ld == 8 * L * C && r_full + l_full > 0) {
+          const int rc = sw ? pass(IC<2>{}, grid, partial, 0, r_full, 0, l_full)
+                            : pass(IC<1>{}, grid, partial, 0, r_full, 0, l_full);
+          if (rc != 0 || (r_full == n_res && l_full == n_lin)) return rc;
+          O3S_CHECK_LAUNCH();
+          slab_rows = grid + 1;
+          return pass(IC<0>{}, 1, partial + (size_t)grid * pstride, r_full, n_res - r_full, l_full, n_lin - l_full);
+        }
+      }
+      return pass(IC<0>{}, grid, partial, 0, n_res, 0, n_lin);
     }
   });
   if (rc != 0) return rc;
-  return launch_finish(partial, grid, pstride, 3 * l.dpad + 3, out, 0, st);
+  return launch_finish(partial, slab_rows, pstride, 3 * l.dpad + 3, out, 0, st);
 }
 
 // ---------------------------------------------------------------------------------

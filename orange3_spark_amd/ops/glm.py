@@ -256,11 +256,16 @@ def glm_grad_synth(n: int, ld: int, d: int, seed: int, row0: int, wtrue: torch.T
 
 # waves/SIMD the mixed kernel is register-allocated for (2 or 3; tools/sweep_glm_mixed.sh)
 MIX_WAVES = int(os.environ.get("O3S_GLM_MIX_WAVES", "3"))
-# waves/SIMD the fused summarizer kernel is compiled for (2: no spill, 3: 6-VGPR spill)
+# waves/SIMD the masked fused summarizer kernel is compiled for (2: no spill, 3: 6-VGPR spill;
+# its mask-free form fits 3 without a spill either way)
 STATS_WAVES = int(os.environ.get("O3S_GLM_STATS_WAVES", "2"))
 # rows per launch slice of a mixed pass (csrc/glm.hip o3s_glm_grad_mixed ``splits``): long
 # passes restart their grid-stride walk every this many rows, at most 16 slices
 MIX_SLICE_ROWS = int(os.environ.get("O3S_GLM_MIX_SLICE_ROWS", str(64 << 20)))
+# whole tiles of a mixed pass (gradient and summarizer) through the mask-free kernel, the
+# ragged rows in a launch of their own (csrc/glm.hip o3s_glm_grad_mixed / o3s_glm_stats_mixed
+# ``full_tiles``); 0: the masked kernel throughout
+MIX_FULL_TILES = int(os.environ.get("O3S_GLM_MIX_FULL", "1"))
 
 
 def mix_splits(n_rows: int) -> int:
@@ -333,7 +338,7 @@ def glm_grad_mixed(X: torch.Tensor, y: torch.Tensor, sw: torch.Tensor | None, n_
                                            cf.data_ptr(), seed & _MASK, row0, n_lin, ws.partial.data_ptr(),
                                            ws.grid, ws.out.data_ptr(), MIX_WAVES, int(res_row0),
                                            N.ptr(t_dev), int(sample_seed) & _MASK, thr, mix_splits(nr + n_lin),
-                                           N.stream_of(X)),
+                                           MIX_FULL_TILES, N.stream_of(X)),
             "glm_grad_mixed")
     return ws.out
 
@@ -353,7 +358,7 @@ def glm_stats_mixed(X: torch.Tensor, y: torch.Tensor, sw: torch.Tensor | None, n
         return glm_stats_torch(X, y, sw, n_lin, d, seed, row0)
     grid = grid or N.num_cus(X.device) * 16   # 16 blocks per CU: 45.9 vs 47.3 ms at 8 (profiles/glm_stats_unweighted_r3.json)
     pstride = 3 * dpad + 4
-    partial = torch.empty(grid * pstride, dtype=torch.float32, device=X.device)
+    partial = torch.empty((grid + 1) * pstride, dtype=torch.float32, device=X.device)   # + the ragged rows' slab row
     out = torch.empty(3 * dpad + 3, dtype=torch.float64, device=X.device)
     if f32_rows(X):
         if n_lin:
@@ -365,7 +370,8 @@ def glm_stats_mixed(X: torch.Tensor, y: torch.Tensor, sw: torch.Tensor | None, n
         N.check(rc, "glm_stats_f32")
         return out
     rc = N.kernels().o3s_glm_stats_mixed(X.data_ptr(), ld, nr, y.data_ptr(), N.ptr(sw), seed & _MASK, row0,
-                                         n_lin, partial.data_ptr(), grid, out.data_ptr(), STATS_WAVES, N.stream_of(X))
+                                         n_lin, partial.data_ptr(), grid, out.data_ptr(), STATS_WAVES, MIX_FULL_TILES,
+                                         N.stream_of(X))
     if rc == -2:
         return None
     N.check(rc, "glm_stats_mixed")
