@@ -363,8 +363,9 @@ class GeneralizedLinearRegression(Estimator, _GLRParams, MLWritable, MLReadable)
         off = None
         if self.isDefined(self.offsetCol) and g(self.offsetCol):
             off = U.numeric_column(df, g(self.offsetCol))
+        from ..ops.gram import column_rows
         r = irls.fit_irls(df.comm, X, y, w, off, fam, lk, g(self.fitIntercept), g(self.regParam), g(self.maxIter),
-                          g(self.tol))
+                          g(self.tol), rows=column_rows(U.features_column(df, g(self.featuresCol)), w))
         m = GeneralizedLinearRegressionModel._from(r.coef, r.intercept)
         m.summary = GeneralizedLinearRegressionTrainingSummary(r, fam.name, X.shape[1], g(self.fitIntercept))
         return m._with_parent(self)

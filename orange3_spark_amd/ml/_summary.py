@@ -327,14 +327,22 @@ class LinearRegressionSummary:
         if self._coef is None:
             raise RuntimeError("coefficient statistics need the model coefficients")
         df = self.predictions
+        from ..ops.gram import column_rows, rows_t_matmul, weighted_gram
         X = df.column_data(self.featuresCol)
-        Xd = (X.dense() if isinstance(X, C.VectorColumn) else X.to_dense(torch.float64)).to(torch.float64)
-        w = df.column_data(self.weightCol).data.to(Xd.device, torch.float64) if self.weightCol else None
-        if self._fit_intercept:
-            Xd = torch.cat([Xd, torch.ones(Xd.shape[0], 1, dtype=torch.float64, device=Xd.device)], 1)
-        Xw = Xd if w is None else Xd * w[:, None]
-        from ..ops.gram import rows_t_matmul
-        G = rows_t_matmul(Xw, Xd)
+        wcol = df.column_data(self.weightCol).data if self.weightCol else None
+        rows = column_rows(X, wcol)
+        if rows is not None:          # one fused pass over the stored rows: [[G, sx], [sx^T, sw]]
+            gs = weighted_gram(rows, X.size, w=wcol)
+            G = gs.G
+            if self._fit_intercept:
+                G = torch.cat([torch.cat([gs.G, gs.sx[:, None]], 1), torch.cat([gs.sx, gs.sw[None]])[None, :]], 0)
+        else:
+            Xd = (X.dense() if isinstance(X, C.VectorColumn) else X.to_dense(torch.float64)).to(torch.float64)
+            w = wcol.to(Xd.device, torch.float64) if wcol is not None else None
+            if self._fit_intercept:
+                Xd = torch.cat([Xd, torch.ones(Xd.shape[0], 1, dtype=torch.float64, device=Xd.device)], 1)
+            Xw = Xd if w is None else Xd * w[:, None]
+            G = rows_t_matmul(Xw, Xd)
         df.comm.all_reduce(G)
         G = G.cpu().numpy()
         dof = self.degreesOfFreedom

@@ -1486,11 +1486,18 @@ class PCA(Estimator, _InOut, MLWritable, MLReadable):
         self._set(**self._input_kwargs)
 
     def _fit(self, df):
-        X = _vec(df, self.getOrDefault(self.inputCol))
-        d = X.shape[1]
-        from ..ops.gram import rows_t_matmul
-        st = torch.cat([rows_t_matmul(X, X).reshape(-1), X.sum(0), torch.tensor([float(X.shape[0])], dtype=X.dtype,
-                                                                                 device=X.device)])
+        from ..ops.gram import column_rows, rows_t_matmul, weighted_gram
+        col = U.features_column(df, self.getOrDefault(self.inputCol))
+        rows = column_rows(col)
+        if rows is not None:          # one fused pass over the stored rows, no fp64 copy
+            d = col.size
+            gs = weighted_gram(rows, d)
+            st = torch.cat([gs.G.reshape(-1), gs.sx, gs.sw.reshape(1)])
+        else:
+            X = _vec(df, self.getOrDefault(self.inputCol))
+            d = X.shape[1]
+            st = torch.cat([rows_t_matmul(X, X).reshape(-1), X.sum(0),
+                            torch.tensor([float(X.shape[0])], dtype=X.dtype, device=X.device)])
         df.comm.all_reduce(st)
         G_, s, n = st[: d * d].reshape(d, d), st[d * d: d * d + d], st[-1]
         mean = s / n

@@ -78,8 +78,11 @@ class LinearRegression(Estimator, _LinearRegressionParams, MLWritable, MLReadabl
         solver = g(self.solver)
         alpha = g(self.elasticNetParam)
         if solver == "normal" or (solver == "auto" and alpha == 0.0 and feat.size <= 4096):
-            coef, b, hist = _normal_equations(comm, U.dense_features(df, g(self.featuresCol)), y, w, g(self.regParam),
-                                              g(self.fitIntercept), g(self.standardization))
+            from ..ops.gram import column_rows
+            rows = column_rows(feat, w)      # stored rows for the fused Gram pass, or None
+            X = rows if rows is not None else U.dense_features(df, g(self.featuresCol))
+            coef, b, hist = _normal_equations(comm, X, y, w, g(self.regParam), g(self.fitIntercept),
+                                              g(self.standardization), d=None if rows is None else feat.size)
             m = LinearRegressionModel._from(coef, b)._with_parent(self)
             m.summary = _linreg_summary(m, df, hist, 0)
             return m
@@ -91,16 +94,24 @@ class LinearRegression(Estimator, _LinearRegressionParams, MLWritable, MLReadabl
         return m
 
 
-def _normal_equations(comm, X, y, w, reg, fit_intercept, standardization):
-    """Weighted ridge via all-reduced sufficient statistics (Spark WeightedLeastSquares)."""
-    Xd = X.to(torch.float64)
-    yd = y.to(torch.float64).to(Xd.device)
-    wd = torch.ones_like(yd) if w is None else w.to(torch.float64).to(Xd.device)
-    D = Xd.shape[1]
-    Xw = Xd * wd[:, None]
-    from ..ops.gram import rows_t_matmul
-    st = torch.cat([rows_t_matmul(Xw, Xd).reshape(-1), rows_t_matmul(Xw, yd), Xw.sum(0), (wd * yd).sum().reshape(1),
-                    wd.sum().reshape(1), (wd * yd * yd).sum().reshape(1)])
+def _normal_equations(comm, X, y, w, reg, fit_intercept, standardization, d=None):
+    """Weighted ridge via all-reduced sufficient statistics (Spark WeightedLeastSquares).
+
+    With ``d`` given, X is the stored rows of the column (logical width d) and the statistics
+    come from one fused pass over them (ops.gram.weighted_gram): no fp64 copy of the table."""
+    from ..ops.gram import rows_t_matmul, weighted_gram
+    if d is not None:
+        D = d
+        gs = weighted_gram(X, d, w, y)
+        st = torch.cat([gs.G.reshape(-1), gs.xty, gs.sx, gs.sy.reshape(1), gs.sw.reshape(1), gs.syy.reshape(1)])
+    else:
+        Xd = X.to(torch.float64)
+        yd = y.to(torch.float64).to(Xd.device)
+        wd = torch.ones_like(yd) if w is None else w.to(torch.float64).to(Xd.device)
+        D = Xd.shape[1]
+        Xw = Xd * wd[:, None]
+        st = torch.cat([rows_t_matmul(Xw, Xd).reshape(-1), rows_t_matmul(Xw, yd), Xw.sum(0),
+                        (wd * yd).sum().reshape(1), wd.sum().reshape(1), (wd * yd * yd).sum().reshape(1)])
     comm.all_reduce(st)
     st = st.cpu().numpy()
     XtX = st[: D * D].reshape(D, D)

@@ -70,8 +70,15 @@ class Correlation:
     @staticmethod
     @ship
     def corr(dataset, column, method="pearson"):
-        X = U.dense_features(dataset, column, torch.float64)
+        from ..ops.gram import column_rows, rows_t_matmul, weighted_gram
         comm = dataset.comm
+        col = U.features_column(dataset, column)
+        rows = column_rows(col) if method == "pearson" else None
+        if rows is not None:          # one fused pass over the stored rows, no fp64 copy
+            gs = weighted_gram(rows, col.size)
+            return Correlation._from_stats(dataset, column, method, comm, col.size,
+                                           torch.cat([gs.G.reshape(-1), gs.sx, gs.sw.reshape(1)]))
+        X = U.dense_features(dataset, column, torch.float64)
         if method == "spearman":
             X = comm.all_gather_v(X) if comm.world_size > 1 else X
             X = X.argsort(0).argsort(0).to(torch.float64)   # ranks (ties broken by order)
@@ -79,9 +86,13 @@ class Correlation:
         else:
             comm_ = comm
         d = X.shape[1]
-        from ..ops.gram import rows_t_matmul
         st = torch.cat([rows_t_matmul(X, X).reshape(-1), X.sum(0), torch.tensor([float(X.shape[0])], dtype=torch.float64,
                                                                        device=X.device)])
+        return Correlation._from_stats(dataset, column, method, comm_, d, st)
+
+    @staticmethod
+    def _from_stats(dataset, column, method, comm_, d, st):
+        """Correlation matrix frame from [G (d * d) | column sums (d) | n] (all-reduced over ``comm_``)."""
         if comm_ is not None:
             comm_.all_reduce(st)
         G, s, n = st[: d * d].reshape(d, d), st[d * d: d * d + d], st[-1]

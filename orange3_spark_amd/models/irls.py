@@ -16,7 +16,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from ..ops.gram import rows_t_matmul
+from ..ops.gram import rows_t_matmul, weighted_gram
 from ..runtime import progress
 
 _DEFAULT_LINK = {"gaussian": "identity", "binomial": "logit", "poisson": "log", "gamma": "inverse"}
@@ -181,7 +181,10 @@ class IrlsResult:
 
 def fit_irls(comm, X: torch.Tensor, y: torch.Tensor, w: torch.Tensor | None, offset: torch.Tensor | None,
              family: Family, link: Link, fit_intercept=True, reg=0.0, max_iter=25, tol=1e-6,
-             chunk=1 << 20) -> IrlsResult:
+             chunk=1 << 20, rows: torch.Tensor | None = None) -> IrlsResult:
+    """``rows``: the stored rows of the feature column (X is their ``[:, :D]`` view) when the fused
+    Gram pass takes them (ops.gram.column_rows): each iteration's normal equations are then one
+    ``weighted_gram`` over them instead of fp64 chunk copies."""
     dev = X.device
     dt = torch.float64
     n, D = X.shape
@@ -193,6 +196,15 @@ def fit_irls(comm, X: torch.Tensor, y: torch.Tensor, w: torch.Tensor | None, off
     def normal_eq(z, ww):
         A = torch.zeros((P, P), dtype=dt, device=dev)
         bvec = torch.zeros(P, dtype=dt, device=dev)
+        if rows is not None:
+            gs = weighted_gram(rows, D, w=ww, y=z)
+            A[:D, :D], bvec[:D] = gs.G, gs.xty
+            if fit_intercept:
+                A[:D, D] = A[D, :D] = gs.sx
+                A[D, D], bvec[D] = gs.sw, gs.sy
+            buf = torch.cat([A.reshape(-1), bvec, gs.sw[None]])
+            comm.all_reduce(buf)
+            return buf[: P * P].reshape(P, P).cpu().numpy(), buf[P * P: P * P + P].cpu().numpy(), float(buf[-1])
         for a in range(0, n, chunk):
             b = min(n, a + chunk)
             Xc = X[a:b].to(dt)

@@ -109,6 +109,8 @@ _SIGS: dict[str, list] = {
     "o3s_assemble_cols": [c_vp, c_i32, c_i32, c_i32, c_i64, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp],
     "o3s_kmeans_update": [c_vp, c_i64, c_i64, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp],
     "o3s_gather_probe": [c_vp, c_i32, c_vp, c_i64, c_i32, c_vp, c_vp],
+    "o3s_gram_layout": [c_i32, C.POINTER(c_i32), C.POINTER(c_i32), C.POINTER(c_i32)],
+    "o3s_gram": [c_vp, c_i32, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp],
 }
 
 
@@ -180,7 +182,7 @@ def host():
 
 
 PRELOAD_TAGS = ("glm", "trees", "kmeans", "als", "als_dense", "als_exact", "assemble", "binsum", "eval",
-                "sampling", "sparse", "text", "probe")
+                "sampling", "sparse", "text", "probe", "gram")
 
 
 def preload(tags=PRELOAD_TAGS) -> dict:
