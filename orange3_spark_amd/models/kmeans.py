@@ -455,8 +455,8 @@ def _fit_kmeans_rows(comm, X, k, max_iter, tol, seed, init, init_steps, initial,
     # screened again -- the others provably keep their centre (exact Lloyd, not an
     # approximation).  The cluster sums are then updated by the rows that changed centre
     # (fp64 running sums, deterministic slab kernel on the changed rows).
-    ham = (HAMERLY and weights is None and ws is not None and K.screen_ok(X) and X.shape[0] > 0
-           and not cosine)
+    ham = (HAMERLY and weights is None and ws is not None and K.screen_ok(X, ((k + 31) // 32) * 32)
+           and X.shape[0] > 0 and not cosine)
     hs = {"a": None, "bnd": None, "S": None, "n": None, "C": None, "ws_sub": None}
     stats_it = []
     for it in range(start + 1, max_iter + 1):

@@ -70,6 +70,7 @@ _SIGS: dict[str, list] = {
     "o3s_kmeans_cost": [c_vp, c_i64, c_i64, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp],
     "o3s_kmeans_bounds": [c_vp, c_vp, c_i64, c_vp, C.c_float, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp],
     "o3s_kmeans_update_ws": [c_i32, c_i32, c_i32, C.POINTER(c_i64), C.POINTER(c_i64), C.POINTER(c_i32)],
+    "o3s_kmeans_screen_lds": [c_i32, c_i32, C.POINTER(c_i32)],
     "o3s_murmur3_terms": [c_vp, c_vp, c_i64, c_u32, c_i64, c_vp, c_vp, c_vp],
     "o3s_als_init": [c_i64, c_i64, c_i32, c_u32, c_i32, c_vp, c_vp],
     "o3s_als_cg": [c_i32, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],

@@ -47,6 +47,11 @@ __device__ __forceinline__ void split_bf16(float v, short& hi, short& lo) {
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
+// XOR-swizzle mask of a row of `slots` 16-B slots: slot ^ (row & mask) must stay inside the
+// row, so the mask covers only the row's power-of-two factor (12 slots: 3, 24 slots: 7 --
+// slots - 1 would send slot 8 of row 16 into the next row), at most `cap`.
+constexpr int swz_mask(int slots, int cap) { return ((slots & -slots) - 1) & cap; }
+
 // x * scale split into two fp16 halves (hi + lo carries ~22 significant bits); the caller
 // picks the power-of-two scale so |x * scale| <= 2^15 (no fp16 overflow)
 __device__ __forceinline__ void split_f16(float v, float scale, short& hi, short& lo) {
@@ -126,7 +131,7 @@ __global__ __launch_bounds__(kAssignThreads, 2) void kmeans_assign_kernel(
       if (rowlist) rowc = rowlist[rowc];        // recheck pass: rows gathered by index
       const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
       const float4 v = 4 * sl < Dx ? *reinterpret_cast<const float4*>(X + rowc * ldx + 4 * sl) : z;
-      *reinterpret_cast<float4*>(xt + rr * D + 4 * (sl ^ (rr & (XS - 1) & 31))) = v;
+      *reinterpret_cast<float4*>(xt + rr * D + 4 * (sl ^ (rr & swz_mask(XS, 31)))) = v;
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the wave reads back only its own slice
   }
@@ -139,7 +144,7 @@ __global__ __launch_bounds__(kAssignThreads, 2) void kmeans_assign_kernel(
       float4 a, b;
       if constexpr (kStageX) {
         const int s0 = (ks * 16 + 8 * h) / 4;
-        const int sw = rr & (XS - 1) & 31;
+        const int sw = rr & swz_mask(XS, 31);
         a = *reinterpret_cast<const float4*>(xt + rr * D + 4 * (s0 ^ sw));
         b = *reinterpret_cast<const float4*>(xt + rr * D + 4 * ((s0 + 1) ^ sw));
       } else {
@@ -190,7 +195,7 @@ __global__ __launch_bounds__(kAssignThreads, 2) void kmeans_assign_kernel(
       const int which = Q / (32 * SLOTS);
       const int rem = Q % (32 * SLOTS);
       const int cr = rem / SLOTS, sw = rem % SLOTS;
-      const int sl = sw ^ (cr & 15 & (SLOTS - 1));
+      const int sl = sw ^ (cr & swz_mask(SLOTS, 15));
       const uint16_t* src = (which ? Clo : Chi) + ((int64_t)(chunk * 32 + cr)) * D + sl * 8;
       __builtin_amdgcn_global_load_lds(src, dbuf + (wid * kWave + k * kAssignThreads) * 8, 16, 0, 0);   // wave-uniform
     }
@@ -261,7 +266,7 @@ __global__ __launch_bounds__(kAssignThreads, 2) void kmeans_assign_kernel(
       // A fragments are read one k-step ahead of the MFMAs that consume them, so the LDS
       // latency hides under the previous step's three MFMAs
       auto afrag = [&](const uint16_t* L, int ks) {
-        const int sw = (ks * 2 + h) ^ (r & 15 & (SLOTS - 1));
+        const int sw = (ks * 2 + h) ^ (r & swz_mask(SLOTS, 15));
         return *reinterpret_cast<const bf16x8*>(L + r * D + sw * 8);
       };
       bf16x8 nh = afrag(Lh, 0), nl = afrag(Ll, 0);
@@ -433,14 +438,14 @@ __global__ __launch_bounds__(kScrThreads, 2) void kmeans_screen_kernel(
     for (int q = 0; q < XL; ++q) {
       const int P = lane + q * kWave;
       const int rr = P / XS, sl = P % XS;
-      *reinterpret_cast<float4*>(xt + rr * D + 4 * (sl ^ (rr & (XS - 1) & 31))) = xv[q];
+      *reinterpret_cast<float4*>(xt + rr * D + 4 * (sl ^ (rr & swz_mask(XS, 31)))) = xv[q];
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     float s = 0.f, e = 0.f;
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       const int s0 = (ks * 16 + 8 * h) / 4;
-      const int sw = r & (XS - 1) & 31;
+      const int sw = r & swz_mask(XS, 31);
       const float4 a = *reinterpret_cast<const float4*>(xt + r * D + 4 * (s0 ^ sw));
       const float4 b = *reinterpret_cast<const float4*>(xt + r * D + 4 * ((s0 + 1) ^ sw));
       const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
@@ -480,7 +485,7 @@ __global__ __launch_bounds__(kScrThreads, 2) void kmeans_screen_kernel(
       if (P >= G * PIECES || stg * G + g >= nchunks) continue;
       const int Q = P % PIECES;
       const int cr = Q / SLOTS, sw = Q % SLOTS;
-      const int sl = sw ^ (cr & 15 & (SLOTS - 1));
+      const int sl = sw ^ (cr & swz_mask(SLOTS, 15));
       __builtin_amdgcn_global_load_lds(sbase + ((g * 32 + cr) * D + sl * 8),
                                        dbuf + (wid * kWave + k * kScrThreads) * 8, 16, 0, 0);   // wave-uniform dst
     }
@@ -557,7 +562,7 @@ __global__ __launch_bounds__(kScrThreads, 2) void kmeans_screen_kernel(
       c0[4 * q + 0] = c4.x; c0[4 * q + 1] = c4.y; c0[4 * q + 2] = c4.z; c0[4 * q + 3] = c4.w;
     }
     auto afrag = [&](int ks) __attribute__((always_inline)) {
-      const int sw = (ks * 2 + h) ^ (r & 15 & (SLOTS - 1));
+      const int sw = (ks * 2 + h) ^ (r & swz_mask(SLOTS, 15));
       return *reinterpret_cast<const bf16x8*>(Lh + r * D + sw * 8);
     };
     float b0[TT];
@@ -590,7 +595,7 @@ __global__ __launch_bounds__(kScrThreads, 2) void kmeans_screen_kernel(
   auto load_frags = [&](const uint16_t* Lh, bf16x8 (&F)[KS]) __attribute__((always_inline)) {
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
-      const int sw = (ks * 2 + h) ^ (r & 15 & (SLOTS - 1));
+      const int sw = (ks * 2 + h) ^ (r & swz_mask(SLOTS, 15));
       F[ks] = *reinterpret_cast<const bf16x8*>(Lh + r * D + sw * 8);
     }
   };
@@ -719,8 +724,11 @@ __global__ __launch_bounds__(kScrThreads, 2) void kmeans_screen_kernel(
     const int idx = take ? oi : myi;
     const float bv = fminf(best[t], ob);
     // a row whose distances never compared (all NaN / inf) keeps an out-of-range index:
-    // clamp it for the loads below; the NaN margin flags the row for the exact re-solve
-    const bool idx_ok = idx >= 0 && idx < Cpad;
+    // clamp it for the loads below; the NaN margin flags the row for the exact re-solve.
+    // A NaN key can also carry the slot of a padding centre (||c||^2 = 2^125): not a
+    // centre either, so the pick a caller without the re-solve keeps stays below K.
+    const bool idx_in = idx >= 0 && idx < Cpad;
+    const bool idx_ok = idx_in && scn[idx_in ? idx : 0] < 0x1p125f;
     int idx2 = idx;
     float thr = INFINITY;
     if (PAIR) {
@@ -873,7 +881,7 @@ __global__ __launch_bounds__(kUpdThreads) void kmeans_update_kernel(
   uint32_t* cnt32 = reinterpret_cast<uint32_t*>(cntw);  // [waves/2][Kp] words
   uint16_t* sorted = cntw + kUpdWaves * Kp;             // [R]
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int seg = R / kUpdWaves;                        // rows per wave segment (multiple of 64)
+  const int seg = R / kUpdWaves;                        // rows per wave segment (a multiple of 64, or 32 at R = 256)
   uint16_t* mycw = cntw + (wid >> 1) * 2 * Kp;          // element (key) at mycw[2*key + (wid&1)]
   const int half = wid & 1;
   float* myslab = slab + (int64_t)blockIdx.x * Kp * D;
@@ -1142,12 +1150,16 @@ template <int D>
 __global__ __launch_bounds__(256) void kmeans_presplit_kernel(const float* __restrict__ X, int64_t n, int64_t ldx,
                                                               int Dx, float xscale, uint4* __restrict__ XP,
                                                               float2* __restrict__ XN) {
-  constexpr int G = D / 8;                     // groups per row (power of two up to 64 lanes)
+  constexpr int G = D / 8;                     // groups per row
+  // a row takes GP lanes, G rounded up to a power of two (D = 96: 12 groups on 16 lanes,
+  // four of them idle), so rows never straddle the butterfly below or a wave
+  constexpr int GP = G <= 4 ? 4 : G <= 8 ? 8 : 16;
+  static_assert(G <= GP, "at most 16 groups per row");
   const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t row = tid / G;
-  const int g = (int)(tid % G);
+  const int64_t row = tid / GP;
+  const int g = (int)(tid % GP);
   float s = 0.f, e = 0.f;
-  if (row < n) {
+  if (row < n && g < G) {
     uint32_t ph[4], pl[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -1168,7 +1180,7 @@ __global__ __launch_bounds__(256) void kmeans_presplit_kernel(const float* __res
     XP[(row * G + g) * 2 + 1] = make_uint4(pl[0], pl[1], pl[2], pl[3]);
   }
 #pragma unroll
-  for (int o = 1; o < G; o <<= 1) {
+  for (int o = 1; o < GP; o <<= 1) {
     s += __shfl_xor(s, o, 64);
     e += __shfl_xor(e, o, 64);
   }
@@ -1184,7 +1196,7 @@ O3S_API int o3s_kmeans_presplit(const float* X, int64_t n, int64_t ldx, int Dx, 
   if (n <= 0) return 0;
   const int D = (Dx + 31) / 32 * 32;
   if (Dx % 4 != 0 || D > 128) return -1;
-  const int64_t threads = n * (D / 8);
+  const int64_t threads = n * (D == 96 ? 16 : D / 8);      // lanes per row: see the kernel's GP
   const dim3 grid((unsigned)((threads + 255) / 256));
   switch (D) {
     case 32: hipLaunchKernelGGL((kmeans_presplit_kernel<32>), grid, dim3(256), 0, st, X, n, ldx, Dx, xscale, (uint4*)XP, XN); break;
@@ -1327,7 +1339,25 @@ O3S_API int o3s_kmeans_bounds(const int32_t* a, float* bnd, int64_t n, const flo
   return 0;
 }
 
-// The screen without row list / bounds (the original entry point).
+// Dynamic LDS of the screen kernel for Dx features and Cpad centres; -3 (as o3s_kmeans_screen2)
+// when it exceeds the 160 KB of a workgroup: the caller takes the split kernel, which reads
+// ||c||^2 from global memory when it does not fit.
+O3S_API int o3s_kmeans_screen_lds(int Dx, int Cpad, int* lds_bytes) {
+  const int D = (Dx + 31) / 32 * 32;
+  size_t b;
+  switch (D / 16) {
+    case 2: b = ScrLds<2>::BYTES; break;
+    case 4: b = ScrLds<4>::BYTES; break;
+    case 6: b = ScrLds<6>::BYTES; break;
+    case 8: b = ScrLds<8>::BYTES; break;
+    case 10: b = ScrLds<10>::BYTES; break;
+    default: *lds_bytes = -1; return -2;
+  }
+  b += sizeof(float) * (size_t)(Cpad > 0 ? Cpad : 0);
+  *lds_bytes = b > 160 * 1024 ? -1 : (int)b;
+  return b > 160 * 1024 ? -3 : 0;
+}
+
 O3S_API int o3s_kmeans_update_ws(int Kp, int D, int grid, int64_t* slab_floats, int64_t* cnt_floats,
                                  int* lds_bytes) {
   const int R = upd_rows(Kp);

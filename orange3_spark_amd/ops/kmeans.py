@@ -170,8 +170,11 @@ def row_bound(X: torch.Tensor, P: "Prepared", xs: float) -> torch.Tensor:
 
 
 def kernel_ok(X: torch.Tensor) -> bool:
+    """Rows the assign / screen / presplit kernels can read as float4: fp32, D % 4 == 0, unit
+    column stride, a row stride of whole float4s and a 16-byte aligned base."""
     return (X.is_cuda and X.dtype == torch.float32 and X.dim() == 2 and X.shape[1] % 4 == 0
-            and X.shape[1] <= MAX_KERNEL_D and X.stride(1) == 1 and X.stride(0) % 4 == 0)
+            and X.shape[1] <= MAX_KERNEL_D and X.stride(1) == 1 and X.stride(0) % 4 == 0
+            and X.data_ptr() % 16 == 0)
 
 
 def update_kernel_ok(X: torch.Tensor) -> bool:
@@ -245,8 +248,16 @@ class _ScreenWs:
 _SWS = _ScreenWs()
 
 
-def screen_ok(X: torch.Tensor) -> bool:
-    return kernel_ok(X) and X.shape[0] < 2 ** 31
+def screen_fits(D: int, Kp: int) -> bool:
+    """Whether the screen kernel's LDS image (staging + ||c||^2 of all Kp padded centres)
+    fits a workgroup for D features -- asked of the native library, which owns the layout."""
+    lds = Ct.c_int()
+    return N.kernels().o3s_kmeans_screen_lds(D, Kp, Ct.byref(lds)) == 0
+
+
+def screen_ok(X: torch.Tensor, Kp: int | None = None) -> bool:
+    """The screen kernel takes X -- and, given the padded centre count, those centres."""
+    return kernel_ok(X) and X.shape[0] < 2 ** 31 and (Kp is None or screen_fits(X.shape[1], Kp))
 
 
 def assign(X: torch.Tensor, C: torch.Tensor, prepared=None, mode: str = "auto", stats: dict | None = None,
@@ -276,9 +287,13 @@ def assign(X: torch.Tensor, C: torch.Tensor, prepared=None, mode: str = "auto", 
     # k-means|| candidate passes (thousands of close candidates: mostly near ties) do not
     # push the later Lloyd iterations (k centres) onto the split path
     key = (id(X), tuple(X.shape), P.hi.shape[0])
+    # more centres than the screen's LDS holds: every screen mode runs the split kernel
+    fits = screen_ok(X, P.hi.shape[0])
+    if mode in ("screen", "pair") and not fits:
+        mode = "split"
     if mode == "auto":
         m, f, cd = _state_get(key, X)
-        if not screen_ok(X):
+        if not fits:
             mode = "split"
         elif m == "split" and cd > 0:
             mode = "split"
@@ -290,7 +305,7 @@ def assign(X: torch.Tensor, C: torch.Tensor, prepared=None, mode: str = "auto", 
         # k-means|| rounds / candidate weights: the screen's pick and its exact fp32 distance
         # are used as they are (a near tie may go to a centre within the screen bound of the
         # nearest -- irrelevant to the sampling probabilities), no re-solve, no host sync
-        mode = "screen" if screen_ok(X) else "split"
+        mode = "screen" if fits else "split"
     if stats is not None:
         stats["mode"] = mode
     if approx and mode == "screen":
@@ -308,7 +323,7 @@ def assign(X: torch.Tensor, C: torch.Tensor, prepared=None, mode: str = "auto", 
                                        st),
                 "kmeans_screen")
         return a, d
-    if mode in ("screen", "pair") and screen_ok(X):
+    if mode in ("screen", "pair") and fits:
         cnt, rows = _SWS.get(n, X.device)
         cnt.zero_()
         tt = SCREEN_TT or (2 if X.shape[1] <= 128 else 1)
@@ -357,16 +372,30 @@ def assign_bounded(X: torch.Tensor, P: Prepared, a: torch.Tensor, bnd: torch.Ten
         return
     lib = N.kernels()
     st = N.stream_of(X)
+    if rows is not None and (rows.dtype != torch.int32 or not rows.is_contiguous()):
+        raise ValueError("rows must be contiguous int32")
+    if bnd.dtype != torch.float32 or tuple(bnd.shape) != (X.shape[0], 2) or not bnd.is_contiguous():
+        raise ValueError("bnd must be fp32 [n, 2]")
+    if not screen_fits(X.shape[1], P.hi.shape[0]):
+        # more centres than the screen's LDS holds: the split kernel on every listed row,
+        # which certifies nothing -- (inf, 0), the bounds of a re-solved near tie
+        N.check(lib.o3s_kmeans_assign(X.data_ptr(), n, X.stride(0), X.shape[1], P.hi.data_ptr(), P.lo.data_ptr(),
+                                      P.cn.data_ptr(), P.hi.shape[0], a.data_ptr(), None, N.ptr(rows), st),
+                "kmeans_assign(bounded)")
+        nb = torch.tensor([float("inf"), 0.0], dtype=torch.float32, device=X.device)
+        if rows is None:
+            bnd[:] = nb
+        else:
+            bnd[rows.long()] = nb
+        if stats is not None:
+            stats["screened"] = stats["flagged"] = n
+        return
     cnt, flag = _SWS.get(n, X.device)
     cnt.zero_()
     xs = x_scale(X)
     eps_x, eps0, eps_e = screen_bound(P, xs, X.shape[1])
     ps = presplit(X, xs)
     tt = SCREEN_TT or (2 if X.shape[1] <= 128 else 1)
-    if rows is not None and (rows.dtype != torch.int32 or not rows.is_contiguous()):
-        raise ValueError("rows must be contiguous int32")
-    if bnd.dtype != torch.float32 or tuple(bnd.shape) != (X.shape[0], 2) or not bnd.is_contiguous():
-        raise ValueError("bnd must be fp32 [n, 2]")
     N.check(lib.o3s_kmeans_screen2(X.data_ptr(), n, X.stride(0), X.shape[1], P.h16.data_ptr(), P.cn.data_ptr(),
                                    P.c32.data_ptr(), P.c32.stride(0), P.hi.shape[0], Ct.c_float(eps_x),
                                    Ct.c_float(eps0), Ct.c_float(eps_e * P.ms), Ct.c_float(xs), Ct.c_float(xs * P.ms),

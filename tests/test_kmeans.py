@@ -77,8 +77,10 @@ def test_gpu_update_matches_index_add(gpu):
 @pytest.mark.gpu
 @pytest.mark.parametrize("k,D", [(2, 128), (7, 64), (300, 200), (4099, 32)])
 def test_gpu_update_small_and_odd_k(gpu, k, D):
-    """Small k gives huge buckets (the stable ballot scatter must stay linear); K=4099 runs
-    with a smaller per-chunk row count; ties to the fp64 index_add reference."""
+    """Small k gives huge buckets (the stable ballot scatter must stay linear); K=4099 leaves
+    the two-blocks-per-CU LDS tier for the one-block tier, still at 16384 rows per chunk (the
+    smaller chunk sizes are covered in test_kmeans_kernel_shapes.py); ties to the fp64
+    index_add reference."""
     g = torch.Generator(device="cpu").manual_seed(k)
     n = 300_001
     X = torch.randn(n, D, generator=g).to(gpu)
