@@ -31,7 +31,7 @@ _SIGS: dict[str, list] = {
     "o3s_glm_grad": [c_i32, c_i32, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_u32, c_i64,
                      c_vp, c_f32, c_vp, c_i32, c_vp, c_i32, c_vp],
     "o3s_glm_grad_mixed": [c_i32, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_u32, c_i64, c_i64,
-                           c_vp, c_i32, c_vp, c_i32, c_i64, c_vp, c_u32, c_u32, c_i32, c_i32, c_vp],
+                           c_vp, c_i32, c_vp, c_i32, c_i64, c_vp, c_u32, c_u32, c_i32, c_i32, c_i32, c_vp],
     "o3s_glm_stats_mixed": [c_vp, c_i64, c_i64, c_vp, c_vp, c_u32, c_i64, c_i64, c_vp, c_i32, c_vp, c_i32, c_i32,
                             c_vp],
     "o3s_glm_grad_f32": [c_i32, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_i32, c_vp, c_i32, c_i64, c_vp,

@@ -12,9 +12,14 @@
 // contiguous -- and the gradient  X^T r  is lane-local (each lane always touches
 // the same 8*CPL columns), so only the per-row dot product needs a cross-lane sum.
 //
-// The op is a GEMV: HBM bound (512 B/row at D=256), so MFMA buys nothing here
-// (SURVEY §7.5 item 2); the budget is bytes.  VALU work per row is ~6x below the
-// HBM-bound cycle budget at 256 CUs, so the kernel runs at the streaming rate.
+// The op is a GEMV (512 B/row at D=256): a pass over resident rows alone runs at the HBM
+// streaming rate (12.9 G rows/s, about 6.6 TB/s; doc/performance.md), and the budget there is
+// bytes.  The mixed pass of a table larger than HBM is not bytes alone: its lineage rows are
+// VALU work (two hashes and eight byte decodes per chunk), per wave it issues VALU in 87 % of
+// its cycles, and its waves spend more than a third of their cycles in s_waitcnt; removing a
+// tenth of its VALU instructions left its cycle count where it was.  What it is held to is
+// the time of its resident rows alone, and the distance to that is load latency a wave does
+// not cover -- see glm_grad_staged_kernel for the schedule built against it.
 //
 // Cross-block reduction: one fp32 slab row per block + `glm_finish` (fp64, fixed
 // order) -> bitwise deterministic results, no float atomics (Guideline 12).
@@ -561,19 +566,122 @@ __host__ __device__ __forceinline__ uint32_t sample_key(uint32_t seed, uint32_t 
   return fmix32(seed ^ fmix32(iter * 0x9E3779B1u + 0x7F4A7C15u));
 }
 
+// The wave-private LDS slot of glm_grad_staged_kernel (the schedule and its wait discipline
+// are described there) and what the wave has in flight into it.  The slot holds the next
+// resident tile as its 8 DMA images of 1 KB (image u * CPL + k = what load (u, k) of
+// grad_tile returns: lane l's 16 B at l * 16, read back by the same lane), then the 64 labels
+// of that tile and the 64 labels of the next lineage tile (lane l's label at l * 4).
+// Every wait and every LDS read of the slot is inline asm: hipcc then sees no LDS load that
+// could alias a DMA target and adds no vmcnt(0) of its own, and the waits count the DMAs
+// exactly.  The only vector-memory operations of the tile loop are the DMAs issued here, in
+// batches of kTileOps (label, then 8 images) and single lineage labels.
+constexpr int kStgTileBytes = 8 * 1024, kStgLabelBytes = kWave * 4;
+constexpr int kStgWaveBytes = kStgTileBytes + 2 * kStgLabelBytes;
+constexpr int kStgLd = 256;            // row width of the one layout that is staged: (8, 4, 2)
+constexpr unsigned kAuxNt = 2;         // cache policy bit "nt", as __builtin_nontemporal_load sets
+struct TileStage {
+  static constexpr int LPR = 8, CPL = 4, UNROLL = 2, G = kWave / LPR, kTileOps = 1 + UNROLL * CPL;
+  // Wave-uniform state only (SGPRs).  What a lane adds -- its byte offset in a tile's rows,
+  // its label's, its LDS addresses -- is recomputed from (g, c) where it is used: held in
+  // registers across the loop, those four values are what makes the lineage tile spill.
+  unsigned char* slot;
+  uint32_t sbase;              // the slot's LDS byte address
+  const unsigned char* xs;     // row 0 of the next resident tile to issue
+  const float* yrs;            // label 0 of the next resident / lineage tile to issue
+  const float* yls;
+  int64_t tstep;               // rows from one tile of this wave to its next
+  uint32_t r_ahead, l_ahead;   // tiles of each role not issued yet
+  // a lineage label is in flight and was issued after the last batch: a wait for that batch
+  // may leave it (vmcnt(1)), and a wait for it drains the batch with it (vmcnt(0))
+  bool lab_younger;
+
+  // (an empty asm per use: otherwise the offsets are hoisted out of the loop as invariants)
+  __device__ static __forceinline__ uint32_t fresh(int v) {
+    asm volatile("" : "+v"(v));
+    return (uint32_t)v;
+  }
+  // the tile row whose label lane (g, c) takes: RowReduce<8, 2>::base(c) * G + g
+  __device__ static __forceinline__ uint32_t label_off(uint32_t g, uint32_t c) { return ((c >> 2) * G + g) * 4; }
+
+  __device__ __forceinline__ void issue_tile(int g, int c) {
+    const uint32_t gg = fresh(g), cc = fresh(c);
+    __builtin_amdgcn_global_load_lds(reinterpret_cast<const unsigned char*>(yrs) + label_off(gg, cc),
+                                     slot + kStgTileBytes, 4, 0, 0);
+    const uint32_t xoff = gg * (kStgLd * 2) + cc * 16;
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u)
+#pragma unroll
+      for (int k = 0; k < CPL; ++k)
+        __builtin_amdgcn_global_load_lds(xs + (u * G * kStgLd * 2 + k * LPR * 16) + xoff, slot + (u * CPL + k) * 1024,
+                                         16, 0, kAuxNt);
+    xs += tstep * (kStgLd * 2);
+    yrs += tstep;
+    --r_ahead;
+    lab_younger = false;
+  }
+  __device__ __forceinline__ void issue_label(int g, int c) {
+    __builtin_amdgcn_global_load_lds(reinterpret_cast<const unsigned char*>(yls) + label_off(fresh(g), fresh(c)),
+                                     slot + kStgTileBytes + kStgLabelBytes, 4, 0, 0);
+    yls += tstep;
+    --l_ahead;
+    lab_younger = true;
+  }
+  // Resident tile: one wait for its batch, the slot read out (lgkmcnt(0): it is rewritten
+  // only after its reads have returned), then the wave's next resident tile issued -- none
+  // after the last, so nothing past the wave's own tiles is ever read.
+  __device__ __forceinline__ void take_tile(int g, int c, short8 (&xv)[UNROLL][CPL], float& yv) {
+    if (lab_younger) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const uint32_t lane = fresh(g) * LPR + fresh(c);
+    asm volatile(
+        "ds_read_b128 %0, %9\n\t"
+        "ds_read_b128 %1, %9 offset:1024\n\t"
+        "ds_read_b128 %2, %9 offset:2048\n\t"
+        "ds_read_b128 %3, %9 offset:3072\n\t"
+        "ds_read_b128 %4, %9 offset:4096\n\t"
+        "ds_read_b128 %5, %9 offset:5120\n\t"
+        "ds_read_b128 %6, %9 offset:6144\n\t"
+        "ds_read_b128 %7, %9 offset:7168\n\t"
+        "ds_read_b32 %8, %10 offset:8192\n\t"
+        "s_waitcnt lgkmcnt(0)"
+        : "=&v"(xv[0][0]), "=&v"(xv[0][1]), "=&v"(xv[0][2]), "=&v"(xv[0][3]), "=&v"(xv[1][0]), "=&v"(xv[1][1]),
+          "=&v"(xv[1][2]), "=&v"(xv[1][3]), "=&v"(yv)
+        : "v"(sbase + lane * 16), "v"(sbase + lane * 4)
+        : "memory");
+    if (r_ahead > 0) issue_tile(g, c);
+    __builtin_amdgcn_sched_barrier(0);   // the DMAs go out ahead of the tile's math
+  }
+  // Lineage tile: its label was issued a lineage tile earlier.  With a batch issued since
+  // (lab_younger false) the wait leaves that batch in flight; otherwise the label is the
+  // youngest operation and the in-order counter leaves no choice but vmcnt(0).
+  __device__ __forceinline__ void take_label(int g, int c, float& yv) {
+    if (lab_younger) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kTileOps) : "memory");
+    const uint32_t a4 = sbase + (fresh(g) * LPR + fresh(c)) * 4;
+    asm volatile("ds_read_b32 %0, %1 offset:8448\n\ts_waitcnt lgkmcnt(0)" : "=v"(yv) : "v"(a4) : "memory");
+    lab_younger = false;
+    if (l_ahead > 0) issue_label(g, c);
+  }
+};
+static_assert(kStgTileBytes == 8192 && kStgLabelBytes == 256, "the asm offsets in TileStage");
+
 // One gradient tile of RT = G * UNROLL rows from source SRC.  Labels / weights come from
 // the materialised label column (y, sw already offset to the role's first row).
 // FULL: every row of the tile is < n and every chunk of the layout is < nch (the caller
 // guarantees both), so rows, chunks and labels are read unclamped and nothing is masked.
-template <class SRC, int LPR, int CPL, int UNROLL, int LOSS, bool SMP, bool FULL = false>
+// STAGED (with FULL, unweighted): rows and labels of a resident tile, and the labels of a
+// lineage tile, come out of the wave's LDS slot (stg); X, y and sw are not read here.
+template <class SRC, int LPR, int CPL, int UNROLL, int LOSS, bool SMP, bool FULL = false, bool STAGED = false>
 __device__ __forceinline__ void grad_tile(
     int64_t base, int64_t n, const typename SRC::elem* __restrict__ X, int64_t ld, int nch,
     const float* __restrict__ y, const float* __restrict__ sw, uint32_t seed, int64_t row0, const float (&w)[CPL][8],
     float wshift, float intercept, int g, int c, const RowSampler smp, float (&acc)[CPL][8], float& rs, float& acc_r,
-    float& acc_loss, float& acc_w) {
+    float& acc_loss, float& acc_w, TileStage* stg = nullptr) {
   constexpr int G = kWave / LPR;
   using RR = RowReduce<LPR, UNROLL>;
   constexpr int NF = RR::NF;
+  static_assert(!STAGED || (FULL && NF == 1 && LPR == TileStage::LPR && CPL == TileStage::CPL && UNROLL == TileStage::UNROLL),
+                "the staged slot holds one (8, 4, 2) tile");
   const int ubase = RR::base(c);
   const bool rep = RR::representative(c);
   typename SRC::chunk xv[UNROLL][CPL];
@@ -588,6 +696,8 @@ __device__ __forceinline__ void grad_tile(
       const int ch = c + k * LPR;
       if constexpr (SRC::kLineage) {
         SRC::decode(synth_word(fk, 2 * ch), synth_word(fk, 2 * ch + 1), xv[u][k]);
+      } else if constexpr (STAGED) {
+        // (read out of the slot below)
       } else if constexpr (FULL) {
         SRC::load(X, ld, row, ch, xv[u][k]);
       } else {
@@ -604,7 +714,10 @@ __device__ __forceinline__ void grad_tile(
     const int64_t row = base + (ubase + j) * G + g;
     const bool ok = row < n;
     const int64_t rowc = ok ? row : n - 1;
-    if constexpr (FULL) {
+    if constexpr (STAGED) {
+      if constexpr (!SRC::kLineage) stg->take_tile(g, c, xv, yy[j]);
+      ww[j] = 1.f;
+    } else if constexpr (FULL) {
       yy[j] = y[row];
       ww[j] = sw ? sw[row] : 1.f;
     } else {
@@ -613,7 +726,7 @@ __device__ __forceinline__ void grad_tile(
       yy[j] = ok ? yv : 0.f;
       ww[j] = ok ? wv : 0.f;
     }
-    if constexpr (SMP) {
+    if constexpr (SMP && !STAGED) {
       if (!smp.keep(row)) ww[j] = 0.f;
     }
   }
@@ -637,6 +750,12 @@ __device__ __forceinline__ void grad_tile(
   constexpr bool kDpp = LPR == 8 && UNROLL == 2;
   if constexpr (kDpp) row_reduce_8x2(dot, c);
   else RR::run(dot, c);
+  if constexpr (STAGED && SRC::kLineage) stg->take_label(g, c, yy[0]);   // as late as the label is needed
+  if constexpr (STAGED && SMP) {   // (and the sampler's hash: a register less across the dot products)
+    // (the lane's row in the tile made opaque: hipcc otherwise keeps grow0 + it, 64 bits per
+    // role, in registers across the loop, which spills)
+    if (!smp.keep(base + (int64_t)TileStage::fresh(ubase * G + g))) ww[0] = 0.f;
+  }
   float res[NF];
 #pragma unroll
   for (int j = 0; j < NF; ++j) {
@@ -669,10 +788,14 @@ __device__ __forceinline__ void grad_tile(
 }
 
 // y / sw hold n_res + n_lin entries: the resident rows' labels, then the lineage rows'.
-// MW: minimum waves per SIMD the register allocator must allow (2 = no constraint at
-// D = 256, 174 VGPRs; 3 = 168 VGPRs with a 4-register spill outside the tile loop).
+// MW: minimum waves per SIMD the register allocator must allow (at D = 256, masked: 2 =
+// 170-175 VGPRs and two waves, 3 = 168 VGPRs with up to 28 B of scratch; mask-free: 163-168
+// VGPRs, no scratch and three waves either way -- the table in doc/performance.md).
 // Every wave walks the interleaved tile sequence (both roles per wave; fixed-role layouts
 // -- some waves regenerating, the others streaming -- measured slower and were removed).
+// A resident tile's loads are issued at its top and waited for a few instructions later, so
+// only the other waves of the SIMD cover their latency; glm_grad_staged_kernel below is the
+// same pass with each wave's next resident tile kept in flight through an LDS slot.
 // FULL: n_res and n_lin are multiples of RT and ld is the layout's full width, so both tile
 // bodies drop their clamps and masks (grad_tile); the host launches the ragged rest apart
 // (o3s_glm_grad_mixed).  The loop holds two tile bodies either way: a third one spills.
@@ -731,6 +854,103 @@ __global__ __launch_bounds__(kBlock, MW) void glm_grad_mixed_kernel(
       rem += r0;
       L += q0;
       if (rem >= S) { rem -= S; ++L; }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < CPL; ++k)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[k][j] = fmaf(rs, kSynthShift, acc[k][j]);
+  grad_epilogue<LPR, CPL>(acc, acc_r, acc_loss, acc_w, partial, pstride, pacc, lane, wid, c);
+}
+
+// The mixed pass with the resident tiles staged through LDS: the (8, 4, 2) layout on whole
+// tiles of 256-column bf16 rows, unweighted (contract of glm_grad_mixed_kernel<8, 4, 2, LOSS,
+// 3, SMP, true> with sw == nullptr; n_res / 16 and n_lin / 16 are below 2^31).
+// Why: a resident tile of glm_grad_mixed_kernel issues its 8 loads at its top and waits for
+// them a few instructions later, and during its lineage tiles a wave has nothing in flight,
+// so the bytes in flight per CU stay well under what three waves per SIMD could hold.  Here a
+// wave issues its NEXT resident tile (label + 8 LDS-DMA images, TileStage) while it takes the
+// current one out of its slot, so those loads stay in flight across the tile's math and the
+// lineage tiles that follow.  A second register copy of a tile does not fit three waves per
+// SIMD; the 8.5 KB slot per wave does (39 KB per block with the epilogue's array).
+// Order: a wave owns the resident tiles gw, gw + nw, ... and the lineage tiles gw, gw + nw,
+// ... (gw its global index, nw the waves of the grid) and interleaves its own two counts by
+// Bresenham, so "next resident tile" is a pointer bump and the mix stays even per wave.  The
+// order is fixed, so the pass is as deterministic as the unstaged one; which wave sums which
+// row differs from it (fp32 block-sum order).
+// Waits (vmcnt completes in order, and the DMAs are the loop's only vector-memory ops):
+//   resident tile: vmcnt(0), or vmcnt(1) when a lineage label was issued after its batch;
+//   lineage tile:  vmcnt(9) for its label when a batch (9 ops) was issued after it, so the
+//                  batch stays in flight; vmcnt(0) when the label is the youngest op -- the
+//                  second of two consecutive lineage tiles, or no resident tile left.
+// wid comes from readfirstlane: the role switch, the guards and the waits are scalar branches.
+// The epilogue's LDS array is a second __shared__ object; it is touched only after the loop,
+// when every DMA has been waited for, so a drain in front of it costs nothing.
+template <int LOSS, bool SMP>
+__global__ __launch_bounds__(kBlock, 3) void glm_grad_staged_kernel(
+    const uint16_t* __restrict__ X, int64_t n_res, const float* __restrict__ y, const float* __restrict__ y_lin,
+    const float* __restrict__ coef, const float* __restrict__ bptr, uint32_t seed, int64_t row0, int64_t n_lin,
+    float* __restrict__ partial, int pstride, int64_t res_row0, const int64_t* __restrict__ t_dev, uint32_t sseed,
+    uint32_t sthr, int pacc) {
+  constexpr int LPR = TileStage::LPR, CPL = TileStage::CPL, UNROLL = TileStage::UNROLL, G = TileStage::G;
+  constexpr int RT = G * UNROLL;
+  constexpr int64_t ld = kStgLd;
+  __shared__ __attribute__((aligned(16))) unsigned char slots[kWavesPerBlock * kStgWaveBytes];
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  const int g = lane / LPR, c = lane % LPR;
+  const float intercept = *bptr;
+  const uint32_t skey = SMP ? sample_key(sseed, (uint32_t)((t_dev ? t_dev[0] : 0) + 1)) : 0u;
+  const RowSampler smp_res{skey, sthr, res_row0}, smp_lin{skey, sthr, row0};
+
+  float w[CPL][8], acc[CPL][8];
+  float wshift = 0.f;
+#pragma unroll
+  for (int k = 0; k < CPL; ++k)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      w[k][j] = coef[8 * (c + k * LPR) + j];
+      wshift += w[k][j];
+      acc[k][j] = 0.f;
+    }
+  wshift *= kSynthShift;
+  float rs = 0.f;
+  float acc_r = 0.f, acc_loss = 0.f, acc_w = 0.f;
+
+  const uint32_t Tr = (uint32_t)(n_res / RT), Tl = (uint32_t)(n_lin / RT);
+  const uint32_t gw = blockIdx.x * kWavesPerBlock + wid, nw = gridDim.x * kWavesPerBlock;
+  const uint32_t nr = gw < Tr ? (Tr - gw + nw - 1) / nw : 0u;     // this wave's tiles of each role
+  const uint32_t nl = gw < Tl ? (Tl - gw + nw - 1) / nw : 0u;
+  const uint32_t S = nr + nl;
+  int64_t br = (int64_t)gw * RT, bl = br;                         // first row of the wave's current tile
+  using lds_byte = __attribute__((address_space(3))) unsigned char;
+  TileStage st{slots + wid * kStgWaveBytes,
+               (uint32_t)(uintptr_t)(lds_byte*)slots + wid * kStgWaveBytes,
+               reinterpret_cast<const unsigned char*>(X + br * ld),
+               y + br,
+               y_lin + bl,
+               (int64_t)nw * RT,
+               nr,
+               nl,
+               false};
+  static_assert(RowReduce<LPR, UNROLL>::NF == 1, "TileStage::label_off: one label per lane");
+  if (nl > 0) st.issue_label(g, c);
+  if (nr > 0) st.issue_tile(g, c);
+  uint32_t rem = 0;
+  for (uint32_t s = 0; s < S; ++s) {
+    // tile s of the wave is a lineage tile iff floor((s + 1) nl / S) > floor(s nl / S)
+    rem += nl;
+    if (rem >= S) {
+      rem -= S;
+      grad_tile<RowsLineage, LPR, CPL, UNROLL, LOSS, SMP, true, true>(bl, n_lin, X, ld, CPL * LPR, y_lin, nullptr, seed, row0,
+                                                                      w, wshift, intercept, g, c, smp_lin, acc, rs, acc_r,
+                                                                      acc_loss, acc_w, &st);
+      bl += st.tstep;
+    } else {
+      grad_tile<RowsBf16, LPR, CPL, UNROLL, LOSS, SMP, true, true>(br, n_res, X, ld, CPL * LPR, y, nullptr, seed, row0, w,
+                                                                   wshift, intercept, g, c, smp_res, acc, rs, acc_r,
+                                                                   acc_loss, acc_w, &st);
+      br += st.tstep;
     }
   }
 #pragma unroll
@@ -1363,11 +1583,14 @@ O3S_API int o3s_glm_grad(int loss, int src, const void* X, int64_t ld, int64_t n
 // run through the mask-free kernel, and the fewer than RT rows that remain of each role go
 // through the masked kernel in one more launch of one block, which adds into slab row 0
 // (pacc; every other slab row stays as the slices left it).  0: masked kernel throughout.
+// staged: 1 = the whole-tile slices of an unweighted pass over the 8x4 layout
+// (256-column rows) that hold rows of both roles run through glm_grad_staged_kernel; 2 = those
+// of one role alone too; every other case, and 0, takes the kernels above.
 O3S_API int o3s_glm_grad_mixed(int loss, const void* X, int64_t ld, int64_t n_res, const float* y,
                                const float* sw, const float* coef, uint32_t seed, int64_t row0,
                                int64_t n_lin, float* partial, int grid, double* out, int waves,
                                int64_t res_row0, const int64_t* t_dev, uint32_t sseed,
-                               uint32_t sthr, int splits, int full_tiles, hipStream_t st) {
+                               uint32_t sthr, int splits, int full_tiles, int staged, hipStream_t st) {
   Layout l;
   if (!resolve_layout(ld, &l) || grid <= 0 || n_res < 0 || n_lin < 0) return -1;
   const int pstride = l.dpad + 4;
@@ -1382,6 +1605,23 @@ O3S_API int o3s_glm_grad_mixed(int loss, const void* X, int64_t ld, int64_t n_re
       if (FULL && (r_n % RT != 0 || l_n % RT != 0 || ld != 8 * L * C)) return -1;
       const float* y_lin = y + n_res + l_lo;
       const float* sw_lin = sw ? sw + n_res + l_lo : nullptr;
+      if constexpr (decltype(FULL)::value && L == TileStage::LPR && C == TileStage::CPL) {
+        static_assert(U == TileStage::UNROLL, "the staged kernel's tile");
+        // whole tiles of the bench layout, unweighted: resident tiles staged through LDS (one
+        // build, 3 waves/SIMD, whatever `waves` says; its tile counters are 32-bit)
+        // (1: slices that hold both roles -- a single role alone measured 3-5 % slower staged
+        // than unstaged, it has no lineage tile to cover; 2: every eligible slice, for tests)
+        const bool wanted = staged >= 2 || (staged == 1 && r_n > 0 && l_n > 0);
+        if (wanted && !sw && r_n / RT < (int64_t(1) << 31) && l_n / RT < (int64_t(1) << 31)) {
+          auto go_staged = [&](auto SMP) {
+            launch(glm_grad_staged_kernel<LOSS, SMP>, g, st, Xh + r_lo * ld, r_n, y + r_lo, y_lin, coef, coef + l.dpad,
+                   seed, row0 + l_lo, l_n, partial, pstride, res_row0 + r_lo, t_dev, sseed, sthr, pacc);
+          };
+          if (smp) go_staged(std::true_type{});
+          else go_staged(std::false_type{});
+          return 0;
+        }
+      }
       auto go = [&](auto MW, auto SMP) {
         launch(glm_grad_mixed_kernel<L, C, U, LOSS, MW, SMP, FULL>, g, st, Xh + r_lo * ld, ld, r_n, y + r_lo,
                sw ? sw + r_lo : nullptr, y_lin, sw_lin, coef, coef + l.dpad, seed, row0 + l_lo, l_n, partial, pstride,

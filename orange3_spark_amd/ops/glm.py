@@ -266,6 +266,12 @@ MIX_SLICE_ROWS = int(os.environ.get("O3S_GLM_MIX_SLICE_ROWS", str(64 << 20)))
 # ragged rows in a launch of their own (csrc/glm.hip o3s_glm_grad_mixed / o3s_glm_stats_mixed
 # ``full_tiles``); 0: the masked kernel throughout
 MIX_FULL_TILES = int(os.environ.get("O3S_GLM_MIX_FULL", "1"))
+# whole tiles of an unweighted gradient pass over 256-column bf16 rows through the
+# kernel that stages each wave's next resident tile in LDS (csrc/glm.hip
+# glm_grad_staged_kernel): 1 = passes that hold resident and lineage rows (where it gains), 2 =
+# passes over one role alone too (3-5 % slower than unstaged; for tests); 0, and every other
+# layout, weighted fits and MIX_FULL_TILES = 0: the unstaged kernels
+MIX_STAGED = int(os.environ.get("O3S_GLM_MIX_STAGED", "1"))
 
 
 def mix_splits(n_rows: int) -> int:
@@ -338,7 +344,7 @@ def glm_grad_mixed(X: torch.Tensor, y: torch.Tensor, sw: torch.Tensor | None, n_
                                            cf.data_ptr(), seed & _MASK, row0, n_lin, ws.partial.data_ptr(),
                                            ws.grid, ws.out.data_ptr(), MIX_WAVES, int(res_row0),
                                            N.ptr(t_dev), int(sample_seed) & _MASK, thr, mix_splits(nr + n_lin),
-                                           MIX_FULL_TILES, N.stream_of(X)),
+                                           MIX_FULL_TILES, MIX_STAGED, N.stream_of(X)),
             "glm_grad_mixed")
     return ws.out
 
