@@ -14,6 +14,8 @@ import torch
 from ..frame import column as C
 from ..frame.dataframe import DataFrame
 from ..models import clustering_extra as CE
+from ..ops import gmm as GM
+from ..ops import gram as GR
 from . import common as U
 from .base import Estimator, Model
 from .linalg import DenseMatrix, DenseVector
@@ -25,6 +27,15 @@ from .util import MLReadable, MLWritable, apply_metadata, mat_col, prim_list, re
 def _float_features(df, name):
     X = U.dense_features(df, name)
     return X.to(torch.float64)
+
+
+def _gmm_rows(df, name, k, w=None):
+    """(stored rows, d) of a vector column the fused E-step (ops/gmm.py) takes as stored -- a
+    plain resident column of a CUDA session, d <= 256, k <= 64, weights absent or non-negative,
+    ``ops.gmm.FUSED`` on -- else None: the caller keeps the chunked fp64 path."""
+    col = U.features_column(df, name)
+    rows = GR.column_rows(col, w) if GM.FUSED else None
+    return (rows, col.size) if rows is not None and GM.estep_ok(rows, col.size, k) else None
 
 
 class _Summary:
@@ -154,7 +165,16 @@ class _GaussianMixtureParams(HasFeaturesCol, HasPredictionCol, HasProbabilityCol
 @register("org.apache.spark.ml.clustering.GaussianMixture")
 class GaussianMixture(Estimator, _GaussianMixtureParams, MLWritable, MLReadable):
     """GaussianMixture clustering. This class performs expectation maximization for
-    multivariate Gaussian Mixture Models (GMMs)."""
+    multivariate Gaussian Mixture Models (GMMs).
+
+    On a GPU session a plain resident vector column of up to 256 features (k <= 64) is fitted
+    on the rows as stored, bf16 or fp32, by a fused E-step kernel and K weighted Gram passes
+    (``ops/gmm.py``); lineage, spilled, sparse and wider columns and CPU sessions run the
+    chunked fp64 path.  The fused path evaluates the per-row log density in fp32, so the
+    log-likelihood carries fp32-level noise (below 1e-8 of its magnitude): the stop rule
+    ``|ll - ll_prev| < tol`` is supported at Spark's default ``tol = 0.01`` and down to roughly
+    that noise; a much smaller ``tol`` is never met there and the fit runs ``maxIter``
+    iterations."""
 
     @keyword_only
     def __init__(self, *, featuresCol="features", predictionCol="prediction", k=2, probabilityCol="probability",
@@ -164,11 +184,12 @@ class GaussianMixture(Estimator, _GaussianMixtureParams, MLWritable, MLReadable)
 
     def _fit(self, df):
         g = self.getOrDefault
-        X = _float_features(df, g(self.featuresCol))
-        r = CE.fit_gmm(df.comm, X, g(self.k), g(self.maxIter), g(self.tol), int(g(self.seed)) & 0xFFFFFFFF,
-                       U.weights_or_none(df, self))
+        w = U.weights_or_none(df, self)
+        stored = _gmm_rows(df, g(self.featuresCol), g(self.k), w)
+        X, d = stored if stored else (_float_features(df, g(self.featuresCol)), None)
+        r = CE.fit_gmm(df.comm, X, g(self.k), g(self.maxIter), g(self.tol), int(g(self.seed)) & 0xFFFFFFFF, w, d=d)
         m = GaussianMixtureModel._from(r.weights, r.means, r.covs)
-        a = m._predict_tensor(X)
+        a = m._predict_tensor(X, d)
         sizes = torch.bincount(a, minlength=g(self.k)).to(torch.float64)
         df.comm.all_reduce(sizes)
         m.summary = _Summary(k=g(self.k), logLikelihood=r.log_likelihood, numIter=r.iterations,
@@ -215,13 +236,22 @@ class GaussianMixtureModel(Model, _GaussianMixtureParams, MLWritable, MLReadable
         cov[:] = [DenseMatrix.from_array(c) for c in self._cov]
         return DataFrame(s.local_view(), OrderedDict(mean=C.ArrayColumn(mean), cov=C.ArrayColumn(cov)))
 
-    def _prob(self, X):
-        dev = X.device
-        lp = CE.gmm_log_prob(X.to(torch.float64), torch.from_numpy(self._mu).to(dev),
-                             torch.from_numpy(self._cov).to(dev), torch.log(torch.from_numpy(self._w).to(dev)))
+    def _on(self, dev):
+        return tuple(torch.from_numpy(a).to(dev) for a in (self._w, self._mu, self._cov))
+
+    def _prob(self, X, d=None):
+        """[n, K] fp64 membership probabilities; with ``d`` given X is the stored rows of
+        :func:`_gmm_rows` and the fused E-step evaluates them."""
+        w, mu, cov = self._on(X.device)
+        if d is not None:
+            P = GM.estep(X, d, w, mu, cov)[0].T.to(torch.float64)
+            return P / P.sum(1, keepdim=True)            # fp32 responsibilities: rows sum to 1 in fp64 again
+        lp = CE.gmm_log_prob(X.to(torch.float64), mu, cov, torch.log(w))
         return torch.softmax(lp, dim=1)
 
-    def _predict_tensor(self, X):
+    def _predict_tensor(self, X, d=None):
+        if d is not None:               # the argmax needs no fp64 copy of the responsibilities
+            return GM.estep(X, d, *self._on(X.device))[0].argmax(0)
         return self._prob(X).argmax(1)
 
     def predict(self, value):
@@ -233,8 +263,8 @@ class GaussianMixtureModel(Model, _GaussianMixtureParams, MLWritable, MLReadable
         return DenseVector(self._prob(x[None, :])[0].cpu().numpy())
 
     def _transform(self, df):
-        X = _float_features(df, self.getOrDefault(self.featuresCol))
-        P = self._prob(X)
+        stored = _gmm_rows(df, self.getOrDefault(self.featuresCol), len(self._w))
+        P = self._prob(*stored) if stored else self._prob(_float_features(df, self.getOrDefault(self.featuresCol)))
         out = df
         if self.getOrDefault(self.probabilityCol):
             out = out.withColumnData(self.getOrDefault(self.probabilityCol), U.vec_out(P))

@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from ..ops import binsum as BS
+from ..ops import gmm as GM
 from ..ops.gram import rows_t_matmul
 from ..ops import sampling
 from . import kmeans as KM
@@ -225,10 +226,16 @@ def _psd(cov: torch.Tensor) -> torch.Tensor:
 
 
 def fit_gmm(comm, X: torch.Tensor, k: int, max_iter: int, tol: float, seed: int, w=None,
-            chunk: int = 1 << 18) -> GMMResult:
+            chunk: int = 1 << 18, d: int | None = None) -> GMMResult:
+    """EM over the local rows X [n, D].  With ``d`` given, X is the stored rows [n, ld >= d] of a
+    vector column that ``ops.gmm.estep_ok`` accepts (or a CPU tensor, which takes the reference
+    ops): every iteration is then one fused E-step and K weighted Gram passes over the rows as
+    stored, with no fp64 copy of the table; the per-row log densities are fp32 there."""
     dev = X.device
-    X = X.to(torch.float64)
-    n, D = X.shape
+    fused = d is not None
+    if not fused:
+        X = X.to(torch.float64)
+    n, D = X.shape[0], (d if fused else X.shape[1])
     rows, N = _rows(comm, n, dev)
     # init (Spark): k groups of 5 random samples -> group means; shared diagonal covariance
     ns = 5
@@ -239,7 +246,7 @@ def fit_gmm(comm, X: torch.Tensor, k: int, max_iter: int, tol: float, seed: int,
     if bool(hit.any()):
         pos = torch.searchsorted(rows[hit], picks).clamp_max(int(hit.sum()) - 1)
         found = rows[hit][pos] == picks
-        S[found] = X[hit][pos[found]]
+        S[found] = X[hit][pos[found]][:, :D].to(torch.float64)       # the k * 5 picked rows only
     comm.all_reduce(S)
     means = S.reshape(k, ns, D).mean(1)
     var = S.var(0, unbiased=False) if k * ns > 1 else torch.ones(D, dtype=torch.float64, device=dev)
@@ -251,23 +258,29 @@ def fit_gmm(comm, X: torch.Tensor, k: int, max_iter: int, tol: float, seed: int,
     it = 0
     for it in range(1, max_iter + 1):
         covs = _psd(covs)
-        Nk = torch.zeros(k, dtype=torch.float64, device=dev)
-        Sk = torch.zeros((k, D), dtype=torch.float64, device=dev)
-        Qk = torch.zeros((k, D, D), dtype=torch.float64, device=dev)
-        ll = torch.zeros((), dtype=torch.float64, device=dev)
-        logw = torch.log(weights.clamp_min(1e-300))
-        for a in range(0, n, chunk):
-            Xc = X[a:a + chunk]
-            lp = gmm_log_prob(Xc, means, covs, logw)
-            lse = torch.logsumexp(lp, dim=1)
-            r = torch.exp(lp - lse[:, None])
-            if wt is not None:
-                r = r * wt[a:a + chunk, None]
-                lse = lse * wt[a:a + chunk]
-            ll += lse.sum()
-            Nk += r.sum(0)
-            Sk += rows_t_matmul(r, Xc)
-            Qk += torch.stack([rows_t_matmul(Xc * r[:, j:j + 1], Xc) for j in range(k)])
+        if fused:
+            resp, lse = GM.estep(X, D, weights, means, covs, wt)
+            lse = lse.to(torch.float64)                # 4 B per row in, not the table
+            ll = (lse if wt is None else lse * wt).sum()
+            Nk, Sk, Qk = GM.mstep(X, D, resp)
+        else:
+            Nk = torch.zeros(k, dtype=torch.float64, device=dev)
+            Sk = torch.zeros((k, D), dtype=torch.float64, device=dev)
+            Qk = torch.zeros((k, D, D), dtype=torch.float64, device=dev)
+            ll = torch.zeros((), dtype=torch.float64, device=dev)
+            logw = torch.log(weights.clamp_min(1e-300))
+            for a in range(0, n, chunk):
+                Xc = X[a:a + chunk]
+                lp = gmm_log_prob(Xc, means, covs, logw)
+                lse = torch.logsumexp(lp, dim=1)
+                r = torch.exp(lp - lse[:, None])
+                if wt is not None:
+                    r = r * wt[a:a + chunk, None]
+                    lse = lse * wt[a:a + chunk]
+                ll += lse.sum()
+                Nk += r.sum(0)
+                Sk += rows_t_matmul(r, Xc)
+                Qk += torch.stack([rows_t_matmul(Xc * r[:, j:j + 1], Xc) for j in range(k)])
         buf = torch.cat([Nk, Sk.reshape(-1), Qk.reshape(-1), ll[None]])
         comm.all_reduce(buf)
         Nk = buf[:k]

@@ -112,6 +112,8 @@ _SIGS: dict[str, list] = {
     "o3s_gather_probe": [c_vp, c_i32, c_vp, c_i64, c_i32, c_vp, c_vp],
     "o3s_gram_layout": [c_i32, C.POINTER(c_i32), C.POINTER(c_i32), C.POINTER(c_i32)],
     "o3s_gram": [c_vp, c_i32, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp],
+    "o3s_gmm_layout": [c_i32, c_i32, C.POINTER(c_i32), C.POINTER(c_i32), C.POINTER(c_i64), C.POINTER(c_i32)],
+    "o3s_gmm_estep": [c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp],
 }
 
 
@@ -183,7 +185,7 @@ def host():
 
 
 PRELOAD_TAGS = ("glm", "trees", "kmeans", "als", "als_dense", "als_exact", "assemble", "binsum", "eval",
-                "sampling", "sparse", "text", "probe", "gram")
+                "sampling", "sparse", "text", "probe", "gram", "gmm")
 
 
 def preload(tags=PRELOAD_TAGS) -> dict:

@@ -12,9 +12,10 @@ fp64 matrix peak).  Host tensors take the plain product.
 delivers G = X^T W X, sx, xty, sw, sy and syy in fp64 with no fp64 copy of the table.  On it
 (for a plain resident vector column of a CUDA session that :func:`gram_kernel_ok` accepts):
 LinearRegression's normal equations, PCA, Correlation.corr (pearson), the IRLS step of
-GeneralizedLinearRegression and the coefficient-inference summary.  Still on
-``rows_t_matmul``: the GMM M-step, NaiveBayes, lineage and spilled columns, d > 256, CPU
-sessions, and spearman correlation (its operand is a rank matrix, not the stored rows).
+GeneralizedLinearRegression, the coefficient-inference summary and the GaussianMixture M-step
+(``ops/gmm.py::mstep``: one pass per component, its responsibilities as the weights).  Still on
+``rows_t_matmul``: NaiveBayes, lineage and spilled columns, d > 256, CPU sessions, and
+spearman correlation (its operand is a rank matrix, not the stored rows).
 """
 from __future__ import annotations
 
