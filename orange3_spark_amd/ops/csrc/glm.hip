@@ -15,11 +15,12 @@
 // The op is a GEMV (512 B/row at D=256): a pass over resident rows alone runs at the HBM
 // streaming rate (12.9 G rows/s, about 6.6 TB/s; doc/performance.md), and the budget there is
 // bytes.  The mixed pass of a table larger than HBM is not bytes alone: its lineage rows are
-// VALU work (two hashes and eight byte decodes per chunk), per wave it issues VALU in 87 % of
-// its cycles, and its waves spend more than a third of their cycles in s_waitcnt; removing a
-// tenth of its VALU instructions left its cycle count where it was.  What it is held to is
-// the time of its resident rows alone, and the distance to that is load latency a wave does
-// not cover -- see glm_grad_staged_kernel for the schedule built against it.
+// VALU work (two hashes and eight byte decodes per chunk).  What it is held to is the time of
+// its resident rows alone.  glm_grad_staged_kernel keeps each wave's next resident tile in
+// flight through an LDS slot, which took the waves' s_waitcnt share from a third of their
+// cycles to a tenth and left the pass VALU-issue bound (VALU issued in 94 - 96 % of its cycles);
+// since then the resident tiles' dot products run on the matrix cores, which were idle, and
+// the VALU keeps the lineage tiles and X^T r (doc/performance.md has the counters of each step).
 //
 // Cross-block reduction: one fp32 slab row per block + `glm_finish` (fp64, fixed
 // order) -> bitwise deterministic results, no float atomics (Guideline 12).
@@ -566,26 +567,51 @@ __host__ __device__ __forceinline__ uint32_t sample_key(uint32_t seed, uint32_t 
   return fmix32(seed ^ fmix32(iter * 0x9E3779B1u + 0x7F4A7C15u));
 }
 
+typedef __bf16 sm_bf16x2 __attribute__((ext_vector_type(2)));
+// Two fp32 -> one dword of two bf16 (round to nearest even: v_cvt_pk_bf16_f32), a in the low half.
+__device__ __forceinline__ uint32_t pk_bf16(float a, float b) {
+  float2_ v;
+  v[0] = a;
+  v[1] = b;
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, sm_bf16x2));
+}
+
 // The wave-private LDS slot of glm_grad_staged_kernel (the schedule and its wait discipline
 // are described there) and what the wave has in flight into it.  The slot holds the next
-// resident tile as its 8 DMA images of 1 KB (image u * CPL + k = what load (u, k) of
-// grad_tile returns: lane l's 16 B at l * 16, read back by the same lane), then the 64 labels
-// of that tile and the 64 labels of the next lineage tile (lane l's label at l * 4).
+// resident tile (16 rows x 32 chunks of 16 B) as its 8 DMA images of 1 KB, then the 64 labels
+// of that tile (lane l holds tile row l & 15's) and the 64 labels of the next lineage tile
+// (lane l's label at l * 4).
+// Placement: image u * CPL + k holds chunks 8k .. 8k + 7 of the rows 8u .. 8u + 7, row 8u + g
+// in the 128 B at g * 128, its chunk 8k + p at position p ^ t(g), t(g) = g >> 1 (lane (g, c')
+// of the DMA fetches chunk 8k + (c' ^ t(g)): every 8 lanes still cover one whole 128-B line).
+// The tile is read out twice with ds_read_b128:
+//   * for X^T r, lane (g, c) takes chunk c + 8k of the rows g and 8 + g, as grad_tile's loads
+//     return them: every read covers 1 KB contiguously, permuted inside 64-B quarters of a
+//     line, which no 16-lane group of ds_read_b128 straddles: conflict-free;
+//   * as the B operand of v_mfma_f32_16x16x32_bf16, lane l takes chunk 8 (l >> 4) + s of tile
+//     row l & 15 in step s.  Unswizzled, the 8 lanes of a 16-lane group that share l >> 4 sit
+//     on 2 of the 16 slots of the 256-B bank row (4-way); with t the 16 rows of a group spread
+//     over 8 slots, rows R and R + 8 together: 2-way.  (s ^ t) = (s & 4) | ((s & 3) ^ t), so
+//     four per-lane bases and the immediate offsets 0 / 64 address the eight steps.
 // Every wait and every LDS read of the slot is inline asm: hipcc then sees no LDS load that
 // could alias a DMA target and adds no vmcnt(0) of its own, and the waits count the DMAs
 // exactly.  The only vector-memory operations of the tile loop are the DMAs issued here, in
 // batches of kTileOps (label, then 8 images) and single lineage labels.
+// Beside the slots the block keeps one image of the coefficients as the A operand of the same
+// MFMA (kStgFragBytes, filled once in the kernel's prologue; see TileStage::dot).
 constexpr int kStgTileBytes = 8 * 1024, kStgLabelBytes = kWave * 4;
 constexpr int kStgWaveBytes = kStgTileBytes + 2 * kStgLabelBytes;
+constexpr int kStgFragBytes = 8 * 1024;   // 8 k-steps x 64 lanes x 16 B
 constexpr int kStgLd = 256;            // row width of the one layout that is staged: (8, 4, 2)
 constexpr unsigned kAuxNt = 2;         // cache policy bit "nt", as __builtin_nontemporal_load sets
 struct TileStage {
   static constexpr int LPR = 8, CPL = 4, UNROLL = 2, G = kWave / LPR, kTileOps = 1 + UNROLL * CPL;
   // Wave-uniform state only (SGPRs).  What a lane adds -- its byte offset in a tile's rows,
-  // its label's, its LDS addresses -- is recomputed from (g, c) where it is used: held in
-  // registers across the loop, those four values are what makes the lineage tile spill.
+  // its label's, its LDS addresses -- is recomputed from the lane id where it is used: held in
+  // registers across the loop, those values are what makes the lineage tile spill.
   unsigned char* slot;
-  uint32_t sbase;              // the slot's LDS byte address
+  uint32_t sbase;              // the slot's LDS byte address (a multiple of 256)
+  uint32_t fbase;              // the coefficient fragments' LDS byte address
   const unsigned char* xs;     // row 0 of the next resident tile to issue
   const float* yrs;            // label 0 of the next resident / lineage tile to issue
   const float* yls;
@@ -603,11 +629,13 @@ struct TileStage {
   // the tile row whose label lane (g, c) takes: RowReduce<8, 2>::base(c) * G + g
   __device__ static __forceinline__ uint32_t label_off(uint32_t g, uint32_t c) { return ((c >> 2) * G + g) * 4; }
 
-  __device__ __forceinline__ void issue_tile(int g, int c) {
-    const uint32_t gg = fresh(g), cc = fresh(c);
-    __builtin_amdgcn_global_load_lds(reinterpret_cast<const unsigned char*>(yrs) + label_off(gg, cc),
+  __device__ __forceinline__ void issue_tile(int lane) {
+    const uint32_t ln = fresh(lane);
+    // (a resident tile's rows are finished in the lanes 0 .. 15, row = lane: TileStage::dot)
+    __builtin_amdgcn_global_load_lds(reinterpret_cast<const unsigned char*>(yrs) + (ln & 15) * 4,
                                      slot + kStgTileBytes, 4, 0, 0);
-    const uint32_t xoff = gg * (kStgLd * 2) + cc * 16;
+    // lane (g, c') = (ln >> 3, ln & 7) fetches chunk c' ^ t(g) of row g (+ 8u, + 8k chunks)
+    const uint32_t xoff = (ln >> 3) * (kStgLd * 2) + ((ln ^ (ln >> 4)) & 7) * 16;
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u)
 #pragma unroll
@@ -629,27 +657,96 @@ struct TileStage {
   // Resident tile: one wait for its batch, the slot read out (lgkmcnt(0): it is rewritten
   // only after its reads have returned), then the wave's next resident tile issued -- none
   // after the last, so nothing past the wave's own tiles is ever read.
-  __device__ __forceinline__ void take_tile(int g, int c, short8 (&xv)[UNROLL][CPL], float& yv) {
+  // xb[s]: the B operand of k-step s (chunk 8 (lane >> 4) + s of tile row lane & 15); xv: the
+  // X^T r layout; yv: the label of tile row lane & 15; fa: the coefficient fragments (A
+  // operand, see dot) of the k-steps 0 - 2.
+  __device__ __forceinline__ void take_tile(int lane, short8 (&xb)[8], short8 (&xv)[UNROLL][CPL], float& yv,
+                                            short8 (&fa)[3]) {
     if (lab_younger) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const uint32_t lane = fresh(g) * LPR + fresh(c);
+    const uint32_t ln = fresh(lane);
+    // operand read: image (R >> 3) * 4 + q, row R & 7, position s ^ t(R), t(R) = (R >> 1) & 3;
+    // sbase is a multiple of 128, so the xor acts on the position bits alone
+    const uint32_t b0 = sbase + ((ln & 8) << 9) + ((ln >> 4) << 10) + ((ln & 7) << 7) + (((ln >> 1) & 3) << 4);
     asm volatile(
-        "ds_read_b128 %0, %9\n\t"
-        "ds_read_b128 %1, %9 offset:1024\n\t"
-        "ds_read_b128 %2, %9 offset:2048\n\t"
-        "ds_read_b128 %3, %9 offset:3072\n\t"
-        "ds_read_b128 %4, %9 offset:4096\n\t"
-        "ds_read_b128 %5, %9 offset:5120\n\t"
-        "ds_read_b128 %6, %9 offset:6144\n\t"
-        "ds_read_b128 %7, %9 offset:7168\n\t"
-        "ds_read_b32 %8, %10 offset:8192\n\t"
+        "ds_read_b128 %17, %26\n\t"
+        "ds_read_b128 %18, %26 offset:1024\n\t"
+        "ds_read_b128 %19, %26 offset:2048\n\t"
+        "ds_read_b128 %0, %20\n\t"
+        "ds_read_b128 %1, %21\n\t"
+        "ds_read_b128 %2, %22\n\t"
+        "ds_read_b128 %3, %23\n\t"
+        "ds_read_b128 %4, %20 offset:64\n\t"
+        "ds_read_b128 %5, %21 offset:64\n\t"
+        "ds_read_b128 %6, %22 offset:64\n\t"
+        "ds_read_b128 %7, %23 offset:64\n\t"
+        "ds_read_b128 %8, %24\n\t"
+        "ds_read_b128 %9, %24 offset:1024\n\t"
+        "ds_read_b128 %10, %24 offset:2048\n\t"
+        "ds_read_b128 %11, %24 offset:3072\n\t"
+        "ds_read_b128 %12, %24 offset:4096\n\t"
+        "ds_read_b128 %13, %24 offset:5120\n\t"
+        "ds_read_b128 %14, %24 offset:6144\n\t"
+        "ds_read_b128 %15, %24 offset:7168\n\t"
+        "ds_read_b32 %16, %25 offset:8192\n\t"
         "s_waitcnt lgkmcnt(0)"
-        : "=&v"(xv[0][0]), "=&v"(xv[0][1]), "=&v"(xv[0][2]), "=&v"(xv[0][3]), "=&v"(xv[1][0]), "=&v"(xv[1][1]),
-          "=&v"(xv[1][2]), "=&v"(xv[1][3]), "=&v"(yv)
-        : "v"(sbase + lane * 16), "v"(sbase + lane * 4)
+        : "=&v"(xb[0]), "=&v"(xb[1]), "=&v"(xb[2]), "=&v"(xb[3]), "=&v"(xb[4]), "=&v"(xb[5]), "=&v"(xb[6]),
+          "=&v"(xb[7]), "=&v"(xv[0][0]), "=&v"(xv[0][1]), "=&v"(xv[0][2]), "=&v"(xv[0][3]), "=&v"(xv[1][0]),
+          "=&v"(xv[1][1]), "=&v"(xv[1][2]), "=&v"(xv[1][3]), "=&v"(yv), "=&v"(fa[0]), "=&v"(fa[1]), "=&v"(fa[2])
+        : "v"(b0), "v"(b0 ^ 16u), "v"(b0 ^ 32u), "v"(b0 ^ 48u), "v"(sbase + ((ln ^ (ln >> 4)) << 4)),
+          "v"(sbase + ln * 4), "v"(fbase + ln * 16)
         : "memory");
-    if (r_ahead > 0) issue_tile(g, c);
+    if (r_ahead > 0) issue_tile(lane);
     __builtin_amdgcn_sched_barrier(0);   // the DMAs go out ahead of the tile's math
+  }
+  // The 16 rows' dot products with the coefficients on the matrix cores: D (16 x 16) = A x B
+  // over eight k-steps of 32 columns.  B is the tile (take_tile's xb); A comes from the block's
+  // fragment image, one ds_read_b128 per step at fbase + s * 1024 + lane * 16: row 0 holds the
+  // coefficients' bf16 hi terms, row 1 the mid and row 2 the lo terms (w = hi + mid + lo
+  // exactly), rows 3 .. 15 zeros.  D has col = lane & 15, row = 4 (lane >> 4) + reg, so the
+  // lanes 0 .. 15 end with their own tile row's three partial dots in d[0], d[1], d[2].
+  // The fragments of the steps 0 - 2 come with the tile reads (take_tile's fa: their latency
+  // hides behind the tile's 16 reads); the steps 3 - 7 are read here, behind the next tile's
+  // DMAs, two steps ahead of their MFMA, each into the buffer of the MFMA issued a step before
+  // (at least 9 wait states earlier).  They are not in the slot and do not gate its reuse.
+  // Nothing inside an asm statement gets hazard padding from the compiler: each dependent MFMA
+  // is at least 9 wait states behind the one before, and the D registers are read by VALU 12
+  // wait states after the last one.
+  __device__ __forceinline__ float4_ dot(int lane, const short8 (&xb)[8], short8 (&fa)[3]) {
+    float4_ d;
+    asm volatile(
+        "v_mfma_f32_16x16x32_bf16 %0, %1, %5, 0\n\t"
+        "s_nop 7\n\t"
+        "ds_read_b128 %1, %4 offset:3072\n\t"
+        "v_mfma_f32_16x16x32_bf16 %0, %2, %6, %0\n\t"
+        "s_nop 7\n\t"
+        "ds_read_b128 %2, %4 offset:4096\n\t"
+        "v_mfma_f32_16x16x32_bf16 %0, %3, %7, %0\n\t"
+        "s_nop 7\n\t"
+        "ds_read_b128 %3, %4 offset:5120\n\t"
+        "s_waitcnt lgkmcnt(2)\n\t"
+        "v_mfma_f32_16x16x32_bf16 %0, %1, %8, %0\n\t"
+        "s_nop 7\n\t"
+        "ds_read_b128 %1, %4 offset:6144\n\t"
+        "s_waitcnt lgkmcnt(2)\n\t"
+        "v_mfma_f32_16x16x32_bf16 %0, %2, %9, %0\n\t"
+        "s_nop 7\n\t"
+        "ds_read_b128 %2, %4 offset:7168\n\t"
+        "s_waitcnt lgkmcnt(2)\n\t"
+        "v_mfma_f32_16x16x32_bf16 %0, %3, %10, %0\n\t"
+        "s_nop 7\n\t"
+        "s_waitcnt lgkmcnt(1)\n\t"
+        "v_mfma_f32_16x16x32_bf16 %0, %1, %11, %0\n\t"
+        "s_nop 7\n\t"
+        "s_waitcnt lgkmcnt(0)\n\t"
+        "v_mfma_f32_16x16x32_bf16 %0, %2, %12, %0\n\t"
+        "s_nop 7\n\t"
+        "s_nop 3"
+        : "=&v"(d), "+v"(fa[0]), "+v"(fa[1]), "+v"(fa[2])
+        : "v"(fbase + fresh(lane) * 16), "v"(xb[0]), "v"(xb[1]), "v"(xb[2]), "v"(xb[3]), "v"(xb[4]), "v"(xb[5]),
+          "v"(xb[6]), "v"(xb[7])
+        : "memory");
+    return d;
   }
   // Lineage tile: its label was issued a lineage tile earlier.  With a batch issued since
   // (lab_younger false) the wait leaves that batch in flight; otherwise the label is the
@@ -669,8 +766,8 @@ static_assert(kStgTileBytes == 8192 && kStgLabelBytes == 256, "the asm offsets i
 // the materialised label column (y, sw already offset to the role's first row).
 // FULL: every row of the tile is < n and every chunk of the layout is < nch (the caller
 // guarantees both), so rows, chunks and labels are read unclamped and nothing is masked.
-// STAGED (with FULL, unweighted): rows and labels of a resident tile, and the labels of a
-// lineage tile, come out of the wave's LDS slot (stg); X, y and sw are not read here.
+// STAGED (with FULL, unweighted, lineage rows): the labels come out of the wave's LDS slot
+// (stg); y and sw are not read here.  (The staged resident tile is staged_resident_tile.)
 template <class SRC, int LPR, int CPL, int UNROLL, int LOSS, bool SMP, bool FULL = false, bool STAGED = false>
 __device__ __forceinline__ void grad_tile(
     int64_t base, int64_t n, const typename SRC::elem* __restrict__ X, int64_t ld, int nch,
@@ -680,14 +777,17 @@ __device__ __forceinline__ void grad_tile(
   constexpr int G = kWave / LPR;
   using RR = RowReduce<LPR, UNROLL>;
   constexpr int NF = RR::NF;
-  static_assert(!STAGED || (FULL && NF == 1 && LPR == TileStage::LPR && CPL == TileStage::CPL && UNROLL == TileStage::UNROLL),
-                "the staged slot holds one (8, 4, 2) tile");
+  static_assert(!STAGED || (SRC::kLineage && FULL && NF == 1 && LPR == TileStage::LPR && CPL == TileStage::CPL &&
+                            UNROLL == TileStage::UNROLL),
+                "the staged slot holds the labels of one (8, 4, 2) lineage tile");
   const int ubase = RR::base(c);
   const bool rep = RR::representative(c);
   typename SRC::chunk xv[UNROLL][CPL];
 #pragma unroll
   for (int u = 0; u < UNROLL; ++u) {
-    const int64_t row = base + u * G + g;
+    // (STAGED: the lane's row group made opaque per tile, or hipcc keeps row0 + g, 64 bits per
+    // lane, across the loop of the staged kernel, which has no register left for it)
+    const int64_t row = base + u * G + (STAGED ? (int)TileStage::fresh(g) : g);
     const bool ok = row < n;
     const int64_t rowc = ok ? row : n - 1;
     const uint32_t fk = SRC::kLineage ? feat_key(seed, row0 + row) : 0u;
@@ -696,8 +796,6 @@ __device__ __forceinline__ void grad_tile(
       const int ch = c + k * LPR;
       if constexpr (SRC::kLineage) {
         SRC::decode(synth_word(fk, 2 * ch), synth_word(fk, 2 * ch + 1), xv[u][k]);
-      } else if constexpr (STAGED) {
-        // (read out of the slot below)
       } else if constexpr (FULL) {
         SRC::load(X, ld, row, ch, xv[u][k]);
       } else {
@@ -715,8 +813,7 @@ __device__ __forceinline__ void grad_tile(
     const bool ok = row < n;
     const int64_t rowc = ok ? row : n - 1;
     if constexpr (STAGED) {
-      if constexpr (!SRC::kLineage) stg->take_tile(g, c, xv, yy[j]);
-      ww[j] = 1.f;
+      ww[j] = 1.f;   // (the label: take_label below)
     } else if constexpr (FULL) {
       yy[j] = y[row];
       ww[j] = sw ? sw[row] : 1.f;
@@ -785,6 +882,51 @@ __device__ __forceinline__ void grad_tile(
       for (int j = 0; j < 8; ++j) acc[k][j] = fmaf(r, x[j], acc[k][j]);
     }
   }
+}
+
+// The resident tile of glm_grad_staged_kernel: 16 rows out of the wave's LDS slot, their dot
+// products on the matrix cores (TileStage::dot), X^T r as in grad_tile.  The rows are finished
+// in the lanes 0 .. 15 (tile row = lane; the other lanes compute on D rows that are zero and
+// add nowhere): margin = (lo + mid) + hi partial dots, one loss_terms for the 16 rows, no
+// cross-lane reduction.  Lane (g, c) then fetches the residuals of its rows g and 8 + g from
+// the lanes g and 8 + g.  base: the tile's first row within the role (the sampler's row index).
+template <int LOSS, bool SMP>
+__device__ __forceinline__ void staged_resident_tile(int64_t base, float intercept, int lane, const RowSampler smp,
+                                                     float (&acc)[TileStage::CPL][8], float& acc_r, float& acc_loss,
+                                                     float& acc_w, TileStage* stg) {
+  constexpr int CPL = TileStage::CPL, UNROLL = TileStage::UNROLL;
+  short8 xb[8], xv[UNROLL][CPL];
+  float yv;
+  short8 fa[3];
+  stg->take_tile(lane, xb, xv, yv, fa);
+  const float4_ d = stg->dot(lane, xb, fa);
+  float wv = 1.f;
+  if constexpr (SMP) {
+    // (the lane's row in the tile made opaque: hipcc otherwise keeps grow0 + it, 64 bits, in
+    // registers across the loop, which spills)
+    if (!smp.keep(base + (int64_t)(TileStage::fresh(lane) & 15u))) wv = 0.f;
+  }
+  float r, l;
+  loss_terms<LOSS>(((d[2] + d[1]) + d[0]) + intercept, yv, wv, r, l);
+  if (lane < 16) { acc_r += r; acc_loss += l; acc_w += wv; }
+#pragma unroll
+  for (int u = 0; u < UNROLL; ++u)
+#pragma unroll
+    for (int k = 0; k < CPL; ++k) RowsBf16::pin(xv[u][k]);
+  // row g's residual sits in lane g, row 8 + g's in lane 8 + g (byte address = 4 * lane)
+  const int src = (int)(TileStage::fresh(lane) >> 3) * 4;
+  const float rr[UNROLL] = {
+      __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(src, __builtin_bit_cast(int, r))),
+      __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(src + 32, __builtin_bit_cast(int, r)))};
+#pragma unroll
+  for (int u = 0; u < UNROLL; ++u)
+#pragma unroll
+    for (int k = 0; k < CPL; ++k) {
+      float x[8];
+      unpack8(xv[u][k], x);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) acc[k][j] = fmaf(rr[u], x[j], acc[k][j]);
+    }
 }
 
 // y / sw hold n_res + n_lin entries: the resident rows' labels, then the lineage rows'.
@@ -872,7 +1014,14 @@ __global__ __launch_bounds__(kBlock, MW) void glm_grad_mixed_kernel(
 // wave issues its NEXT resident tile (label + 8 LDS-DMA images, TileStage) while it takes the
 // current one out of its slot, so those loads stay in flight across the tile's math and the
 // lineage tiles that follow.  A second register copy of a tile does not fit three waves per
-// SIMD; the 8.5 KB slot per wave does (39 KB per block with the epilogue's array).
+// SIMD; the 8.5 KB slot per wave does.
+// The resident tile's 16 dot products are eight v_mfma_f32_16x16x32_bf16 (TileStage::dot,
+// staged_resident_tile): the tile as it lies in the slot is the B operand, the coefficients
+// split into three bf16 terms are the A operand, read from an 8 KB image the block builds
+// once (the products are exact in fp32; only the accumulation order differs from the fp32
+// chain of the unstaged kernels).  The lineage tile's dot and both tiles' X^T r stay on the
+// VALU, on the fp32 w.  LDS per block: 4 slots, the image and the epilogue's array, 47 168 B
+// (three blocks per CU: 141.5 of 160 KB).
 // Order: a wave owns the resident tiles gw, gw + nw, ... and the lineage tiles gw, gw + nw,
 // ... (gw its global index, nw the waves of the grid) and interleaves its own two counts by
 // Bresenham, so "next resident tile" is a pointer bump and the mix stays even per wave.  The
@@ -884,8 +1033,10 @@ __global__ __launch_bounds__(kBlock, MW) void glm_grad_mixed_kernel(
 //                  batch stays in flight; vmcnt(0) when the label is the youngest op -- the
 //                  second of two consecutive lineage tiles, or no resident tile left.
 // wid comes from readfirstlane: the role switch, the guards and the waits are scalar branches.
-// The epilogue's LDS array is a second __shared__ object; it is touched only after the loop,
-// when every DMA has been waited for, so a drain in front of it costs nothing.
+// The coefficient image and the epilogue's array are __shared__ objects of their own: the
+// image is written before the first DMA is issued (one __syncthreads()) and read by inline
+// asm only; the epilogue's array is touched only after the loop, when every DMA has been
+// waited for, so a drain in front of it costs nothing.
 template <int LOSS, bool SMP>
 __global__ __launch_bounds__(kBlock, 3) void glm_grad_staged_kernel(
     const uint16_t* __restrict__ X, int64_t n_res, const float* __restrict__ y, const float* __restrict__ y_lin,
@@ -895,7 +1046,9 @@ __global__ __launch_bounds__(kBlock, 3) void glm_grad_staged_kernel(
   constexpr int LPR = TileStage::LPR, CPL = TileStage::CPL, UNROLL = TileStage::UNROLL, G = TileStage::G;
   constexpr int RT = G * UNROLL;
   constexpr int64_t ld = kStgLd;
-  __shared__ __attribute__((aligned(16))) unsigned char slots[kWavesPerBlock * kStgWaveBytes];
+  __shared__ __attribute__((aligned(256))) unsigned char slots[kWavesPerBlock * kStgWaveBytes];
+  __shared__ __attribute__((aligned(256))) unsigned char frags[kStgFragBytes];
+  static_assert(kStgWaveBytes % 256 == 0, "TileStage: a slot starts on a bank row");
   const int lane = threadIdx.x & (kWave - 1);
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
   const int g = lane / LPR, c = lane % LPR;
@@ -924,8 +1077,33 @@ __global__ __launch_bounds__(kBlock, 3) void glm_grad_staged_kernel(
   const uint32_t S = nr + nl;
   int64_t br = (int64_t)gw * RT, bl = br;                         // first row of the wave's current tile
   using lds_byte = __attribute__((address_space(3))) unsigned char;
+  // The coefficients as the A operand of the resident tiles' MFMAs (TileStage::dot): entry
+  // (step s, lane l) of the image is A[row l & 15][k = 8 (l >> 4) + j] = the bf16 term l & 15
+  // (0 hi, 1 mid, 2 lo, as split8 forms them; zero from 3 on) of the coefficients of chunk
+  // 8 (l >> 4) + s, the chunk that lane l's B operand holds in step s.
+  for (int e = threadIdx.x; e < kStgFragBytes / 16; e += kBlock) {
+    const int s = e >> 6, term = e & 15, q = (e & 63) >> 4;
+    uint32_t p[4] = {0u, 0u, 0u, 0u};
+    if (term < 3) {
+      const float* cw = coef + 8 * (8 * q + s);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float x0 = cw[2 * j], x1 = cw[2 * j + 1];
+        const uint32_t ph = pk_bf16(x0, x1);
+        const float r0 = x0 - __uint_as_float(ph << 16), r1 = x1 - __uint_as_float(ph & 0xffff0000u);
+        const uint32_t pm = pk_bf16(r0, r1);
+        const uint32_t pl = pk_bf16(r0 - __uint_as_float(pm << 16), r1 - __uint_as_float(pm & 0xffff0000u));
+        p[j] = term == 0 ? ph : term == 1 ? pm : pl;
+      }
+    }
+    uint32_t* const dst = reinterpret_cast<uint32_t*>(frags + e * 16);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) dst[j] = p[j];
+  }
+  __syncthreads();   // (ahead of the first DMA: a barrier drains vmcnt)
   TileStage st{slots + wid * kStgWaveBytes,
                (uint32_t)(uintptr_t)(lds_byte*)slots + wid * kStgWaveBytes,
+               (uint32_t)(uintptr_t)(lds_byte*)frags,
                reinterpret_cast<const unsigned char*>(X + br * ld),
                y + br,
                y_lin + bl,
@@ -935,7 +1113,7 @@ __global__ __launch_bounds__(kBlock, 3) void glm_grad_staged_kernel(
                false};
   static_assert(RowReduce<LPR, UNROLL>::NF == 1, "TileStage::label_off: one label per lane");
   if (nl > 0) st.issue_label(g, c);
-  if (nr > 0) st.issue_tile(g, c);
+  if (nr > 0) st.issue_tile(lane);
   uint32_t rem = 0;
   for (uint32_t s = 0; s < S; ++s) {
     // tile s of the wave is a lineage tile iff floor((s + 1) nl / S) > floor(s nl / S)
@@ -947,9 +1125,7 @@ __global__ __launch_bounds__(kBlock, 3) void glm_grad_staged_kernel(
                                                                       acc_loss, acc_w, &st);
       bl += st.tstep;
     } else {
-      grad_tile<RowsBf16, LPR, CPL, UNROLL, LOSS, SMP, true, true>(br, n_res, X, ld, CPL * LPR, y, nullptr, seed, row0, w,
-                                                                   wshift, intercept, g, c, smp_res, acc, rs, acc_r,
-                                                                   acc_loss, acc_w, &st);
+      staged_resident_tile<LOSS, SMP>(br, intercept, lane, smp_res, acc, acc_r, acc_loss, acc_w, &st);
       br += st.tstep;
     }
   }
@@ -2297,15 +2473,6 @@ O3S_API int o3s_glm_colstats_f32(const void* X, int64_t ld, int64_t n, const flo
 namespace {
 
 typedef uint32_t sm_u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 sm_bf16x2 __attribute__((ext_vector_type(2)));
-
-// Two fp32 -> one dword of two bf16 (round to nearest even: v_cvt_pk_bf16_f32), a in the low half.
-__device__ __forceinline__ uint32_t pk_bf16(float a, float b) {
-  float2_ v;
-  v[0] = a;
-  v[1] = b;
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, sm_bf16x2));
-}
 
 // 8 fp32 -> bf16 terms hi + mid + lo (each the rounding of the exact remainder so far):
 // x - (hi + mid + lo) is below 2^-25 |x|, x - (hi + mid) below 2^-17 |x|.
