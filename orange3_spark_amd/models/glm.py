@@ -83,7 +83,9 @@ class GlmData:
         # (ops.glm.glm_grad_mixed): 46-47 ms for the same pass
         # (profiles/glm_mixed_sweep.json).  The grid is 32 blocks per CU: the dispatcher
         # then balances CUs that stream at different speeds (a persistent one-wave-set
-        # grid was 8-10 % slower).
+        # grid with a static assignment was 8-10 % slower).  A staged pass large enough
+        # (ops.glm.MIX_PERSIST) runs instead as one launch of persistent waves that
+        # claim row items from a ticket; that launch sizes its own grid.
         self.overlap = None
         # (also without lineage rows: its LPR = 8 lane mapping streams 6.7 TB/s vs 6.4 TB/s
         # for glm_grad's, tools/bench_glm_roles.py)
@@ -124,6 +126,9 @@ class GlmData:
             grid = max(1, min(cus * 32, -(-tiles // 4)))
             self.ws = G.GlmWorkspace(self.device, self.ld,
                                      grid=int(os.environ.get("O3S_GLM_GRID_MIX", str(grid))))
+            # the persistent pass's item slab, if these rows take it, now and not in the first pass
+            self.ws.reserve_items(int(self.X.shape[0]), int(self.lineage[2] if self.lineage else 0),
+                                  self.sw is not None)
         elif self.kernel and self.lineage and self.X.shape[0] and os.environ.get("O3S_GLM_OVERLAP", "1") == "1":
             cus = N.num_cus(self.device)
             res_grid = int(os.environ.get("O3S_GLM_GRID_RES", str(cus * 8)))

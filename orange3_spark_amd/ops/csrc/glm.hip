@@ -21,6 +21,9 @@
 // cycles to a tenth and left the pass VALU-issue bound (VALU issued in 94 - 96 % of its cycles);
 // since then the resident tiles' dot products run on the matrix cores, which were idle, and
 // the VALU keeps the lineage tiles and X^T r (doc/performance.md has the counters of each step).
+// A pass large enough runs that kernel's tiles as ONE launch of persistent waves that claim row
+// items from a ticket (glm_grad_persist_kernel, glm_items.h), which fills the wave slots that
+// the blocks of 14 sliced launches left empty between their prologues and epilogues.
 //
 // Cross-block reduction: one fp32 slab row per block + `glm_finish` (fp64, fixed
 // order) -> bitwise deterministic results, no float atomics (Guideline 12).
@@ -33,6 +36,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "glm_items.h"
 
 using namespace o3s;
 
@@ -620,6 +624,15 @@ struct TileStage {
   // a lineage label is in flight and was issued after the last batch: a wait for that batch
   // may leave it (vmcnt(1)), and a wait for it drains the batch with it (vmcnt(0))
   bool lab_younger;
+  // glm_grad_persist_kernel only (PERSIST in take_tile / take_label; zero and unused elsewhere):
+  // the bases of the pass's three arrays, the next item's first tiles and counts (nx_nr / nx_nl
+  // are zero until that item is known and again once the stager has moved on to it), and
+  // whether the first batch / label of the next item is already in flight.
+  const unsigned char* x0;
+  const float* yr0;
+  const float* yl0;
+  uint32_t nx_r0, nx_nr, nx_l0, nx_nl;
+  bool r_pre, l_pre;
 
   // (an empty asm per use: otherwise the offsets are hoisted out of the loop as invariants)
   __device__ static __forceinline__ uint32_t fresh(int v) {
@@ -660,6 +673,8 @@ struct TileStage {
   // xb[s]: the B operand of k-step s (chunk 8 (lane >> 4) + s of tile row lane & 15); xv: the
   // X^T r layout; yv: the label of tile row lane & 15; fa: the coefficient fragments (A
   // operand, see dot) of the k-steps 0 - 2.
+  // PERSIST: after the last tile of the item the stager moves on to the next item's first.
+  template <bool PERSIST = false>
   __device__ __forceinline__ void take_tile(int lane, short8 (&xb)[8], short8 (&xv)[UNROLL][CPL], float& yv,
                                             short8 (&fa)[3]) {
     if (lab_younger) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
@@ -696,6 +711,15 @@ struct TileStage {
         : "v"(b0), "v"(b0 ^ 16u), "v"(b0 ^ 32u), "v"(b0 ^ 48u), "v"(sbase + ((ln ^ (ln >> 4)) << 4)),
           "v"(sbase + ln * 4), "v"(fbase + ln * 16)
         : "memory");
+    if constexpr (PERSIST) {
+      if (r_ahead == 0 && nx_nr > 0) {
+        xs = x0 + (uint64_t)nx_r0 * (UNROLL * G * kStgLd * 2);
+        yrs = yr0 + (uint64_t)nx_r0 * (UNROLL * G);
+        r_ahead = nx_nr;
+        nx_nr = 0;
+        r_pre = true;
+      }
+    }
     if (r_ahead > 0) issue_tile(lane);
     __builtin_amdgcn_sched_barrier(0);   // the DMAs go out ahead of the tile's math
   }
@@ -751,12 +775,21 @@ struct TileStage {
   // Lineage tile: its label was issued a lineage tile earlier.  With a batch issued since
   // (lab_younger false) the wait leaves that batch in flight; otherwise the label is the
   // youngest operation and the in-order counter leaves no choice but vmcnt(0).
+  template <bool PERSIST = false>
   __device__ __forceinline__ void take_label(int g, int c, float& yv) {
     if (lab_younger) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kTileOps) : "memory");
     const uint32_t a4 = sbase + (fresh(g) * LPR + fresh(c)) * 4;
     asm volatile("ds_read_b32 %0, %1 offset:8448\n\ts_waitcnt lgkmcnt(0)" : "=v"(yv) : "v"(a4) : "memory");
     lab_younger = false;
+    if constexpr (PERSIST) {
+      if (l_ahead == 0 && nx_nl > 0) {
+        yls = yl0 + (uint64_t)nx_l0 * (UNROLL * G);
+        l_ahead = nx_nl;
+        nx_nl = 0;
+        l_pre = true;
+      }
+    }
     if (l_ahead > 0) issue_label(g, c);
   }
 };
@@ -768,7 +801,8 @@ static_assert(kStgTileBytes == 8192 && kStgLabelBytes == 256, "the asm offsets i
 // guarantees both), so rows, chunks and labels are read unclamped and nothing is masked.
 // STAGED (with FULL, unweighted, lineage rows): the labels come out of the wave's LDS slot
 // (stg); y and sw are not read here.  (The staged resident tile is staged_resident_tile.)
-template <class SRC, int LPR, int CPL, int UNROLL, int LOSS, bool SMP, bool FULL = false, bool STAGED = false>
+template <class SRC, int LPR, int CPL, int UNROLL, int LOSS, bool SMP, bool FULL = false, bool STAGED = false,
+          bool PERSIST = false>
 __device__ __forceinline__ void grad_tile(
     int64_t base, int64_t n, const typename SRC::elem* __restrict__ X, int64_t ld, int nch,
     const float* __restrict__ y, const float* __restrict__ sw, uint32_t seed, int64_t row0, const float (&w)[CPL][8],
@@ -847,7 +881,7 @@ __device__ __forceinline__ void grad_tile(
   constexpr bool kDpp = LPR == 8 && UNROLL == 2;
   if constexpr (kDpp) row_reduce_8x2(dot, c);
   else RR::run(dot, c);
-  if constexpr (STAGED && SRC::kLineage) stg->take_label(g, c, yy[0]);   // as late as the label is needed
+  if constexpr (STAGED && SRC::kLineage) stg->template take_label<PERSIST>(g, c, yy[0]);   // as late as the label is needed
   if constexpr (STAGED && SMP) {   // (and the sampler's hash: a register less across the dot products)
     // (the lane's row in the tile made opaque: hipcc otherwise keeps grow0 + it, 64 bits per
     // role, in registers across the loop, which spills)
@@ -890,7 +924,7 @@ __device__ __forceinline__ void grad_tile(
 // add nowhere): margin = (lo + mid) + hi partial dots, one loss_terms for the 16 rows, no
 // cross-lane reduction.  Lane (g, c) then fetches the residuals of its rows g and 8 + g from
 // the lanes g and 8 + g.  base: the tile's first row within the role (the sampler's row index).
-template <int LOSS, bool SMP>
+template <int LOSS, bool SMP, bool PERSIST = false>
 __device__ __forceinline__ void staged_resident_tile(int64_t base, float intercept, int lane, const RowSampler smp,
                                                      float (&acc)[TileStage::CPL][8], float& acc_r, float& acc_loss,
                                                      float& acc_w, TileStage* stg) {
@@ -898,7 +932,7 @@ __device__ __forceinline__ void staged_resident_tile(int64_t base, float interce
   short8 xb[8], xv[UNROLL][CPL];
   float yv;
   short8 fa[3];
-  stg->take_tile(lane, xb, xv, yv, fa);
+  stg->template take_tile<PERSIST>(lane, xb, xv, yv, fa);
   const float4_ d = stg->dot(lane, xb, fa);
   float wv = 1.f;
   if constexpr (SMP) {
@@ -1005,6 +1039,33 @@ __global__ __launch_bounds__(kBlock, MW) void glm_grad_mixed_kernel(
   grad_epilogue<LPR, CPL>(acc, acc_r, acc_loss, acc_w, partial, pstride, pacc, lane, wid, c);
 }
 
+// The coefficients as the A operand of the resident tiles' MFMAs (TileStage::dot): entry
+// (step s, lane l) of the image is A[row l & 15][k = 8 (l >> 4) + j] = the bf16 term l & 15
+// (0 hi, 1 mid, 2 lo, as split8 forms them; zero from 3 on) of the coefficients of chunk
+// 8 (l >> 4) + s, the chunk that lane l's B operand holds in step s.
+// Written by the whole block; the caller's __syncthreads() stands between it and the first read.
+__device__ __forceinline__ void build_coef_frags(unsigned char* __restrict__ frags, const float* __restrict__ coef) {
+  for (int e = threadIdx.x; e < kStgFragBytes / 16; e += kBlock) {
+    const int s = e >> 6, term = e & 15, q = (e & 63) >> 4;
+    uint32_t p[4] = {0u, 0u, 0u, 0u};
+    if (term < 3) {
+      const float* cw = coef + 8 * (8 * q + s);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float x0 = cw[2 * j], x1 = cw[2 * j + 1];
+        const uint32_t ph = pk_bf16(x0, x1);
+        const float r0 = x0 - __uint_as_float(ph << 16), r1 = x1 - __uint_as_float(ph & 0xffff0000u);
+        const uint32_t pm = pk_bf16(r0, r1);
+        const uint32_t pl = pk_bf16(r0 - __uint_as_float(pm << 16), r1 - __uint_as_float(pm & 0xffff0000u));
+        p[j] = term == 0 ? ph : term == 1 ? pm : pl;
+      }
+    }
+    uint32_t* const dst = reinterpret_cast<uint32_t*>(frags + e * 16);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) dst[j] = p[j];
+  }
+}
+
 // The mixed pass with the resident tiles staged through LDS: the (8, 4, 2) layout on whole
 // tiles of 256-column bf16 rows, unweighted (contract of glm_grad_mixed_kernel<8, 4, 2, LOSS,
 // 3, SMP, true> with sw == nullptr; n_res / 16 and n_lin / 16 are below 2^31).
@@ -1077,29 +1138,7 @@ __global__ __launch_bounds__(kBlock, 3) void glm_grad_staged_kernel(
   const uint32_t S = nr + nl;
   int64_t br = (int64_t)gw * RT, bl = br;                         // first row of the wave's current tile
   using lds_byte = __attribute__((address_space(3))) unsigned char;
-  // The coefficients as the A operand of the resident tiles' MFMAs (TileStage::dot): entry
-  // (step s, lane l) of the image is A[row l & 15][k = 8 (l >> 4) + j] = the bf16 term l & 15
-  // (0 hi, 1 mid, 2 lo, as split8 forms them; zero from 3 on) of the coefficients of chunk
-  // 8 (l >> 4) + s, the chunk that lane l's B operand holds in step s.
-  for (int e = threadIdx.x; e < kStgFragBytes / 16; e += kBlock) {
-    const int s = e >> 6, term = e & 15, q = (e & 63) >> 4;
-    uint32_t p[4] = {0u, 0u, 0u, 0u};
-    if (term < 3) {
-      const float* cw = coef + 8 * (8 * q + s);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float x0 = cw[2 * j], x1 = cw[2 * j + 1];
-        const uint32_t ph = pk_bf16(x0, x1);
-        const float r0 = x0 - __uint_as_float(ph << 16), r1 = x1 - __uint_as_float(ph & 0xffff0000u);
-        const uint32_t pm = pk_bf16(r0, r1);
-        const uint32_t pl = pk_bf16(r0 - __uint_as_float(pm << 16), r1 - __uint_as_float(pm & 0xffff0000u));
-        p[j] = term == 0 ? ph : term == 1 ? pm : pl;
-      }
-    }
-    uint32_t* const dst = reinterpret_cast<uint32_t*>(frags + e * 16);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) dst[j] = p[j];
-  }
+  build_coef_frags(frags, coef);
   __syncthreads();   // (ahead of the first DMA: a barrier drains vmcnt)
   TileStage st{slots + wid * kStgWaveBytes,
                (uint32_t)(uintptr_t)(lds_byte*)slots + wid * kStgWaveBytes,
@@ -1134,6 +1173,230 @@ __global__ __launch_bounds__(kBlock, 3) void glm_grad_staged_kernel(
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc[k][j] = fmaf(rs, kSynthShift, acc[k][j]);
   grad_epilogue<LPR, CPL>(acc, acc_r, acc_loss, acc_w, partial, pstride, pacc, lane, wid, c);
+}
+
+// One lane takes the next ticket (a vector atomic with return); every lane gets its value.
+__device__ __forceinline__ uint32_t claim_item(uint32_t* __restrict__ ticket, int lane) {
+  uint32_t t = 0;
+  if (lane == 0) t = atomicAdd(ticket, 1u);
+  return (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
+}
+// Item i of the pass, wave-uniform (SGPRs).
+__device__ __forceinline__ GlmItem uniform_item(uint32_t i, uint32_t Tr, uint32_t Tl, uint32_t items, double inv) {
+  const GlmItem it = glm_item(i, Tr, Tl, items, inv);
+  return GlmItem{(uint32_t)__builtin_amdgcn_readfirstlane((int)it.r0), (uint32_t)__builtin_amdgcn_readfirstlane((int)it.nr),
+                 (uint32_t)__builtin_amdgcn_readfirstlane((int)it.l0), (uint32_t)__builtin_amdgcn_readfirstlane((int)it.nl)};
+}
+// End of an item: the wave's sums over its 8 row groups, written in full to the item's slab
+// row [X^T r (DP) | sum r | loss | weight sum]; the accumulators start the next item at zero.
+// The 32 column sums of a lane are reduced by recursive halving over the three group bits of
+// the lane id (lane ^ 32, ^ 16, ^ 8): at each step a lane keeps one half of its values, sends
+// the other half to its partner and adds what the partner sends -- 16 + 8 + 4 exchanges
+// instead of the 96 of a butterfly over all 32 -- and ends with the complete sums of four
+// consecutive columns, chunk c + 8 k, k = (g >> 1) & 3, floats 4 (g & 1) .. + 3: one 16-B
+// store per lane covers the 256 columns.  The order is fixed (a function of the lane id).
+template <int LPR, int CPL>
+__device__ __forceinline__ void item_flush(float (&acc)[CPL][8], float& rs, float& acc_r, float& acc_loss,
+                                           float& acc_w, float* __restrict__ dst, int lane) {
+  static_assert(LPR == 8 && CPL == 4, "the halving below is written for the (8, 4) layout");
+  constexpr int DP = LPR * CPL * 8;
+  float a[16], b[8];
+  float4_ q;
+  // (the lane id made opaque here: what is derived from it -- the three selects, the store's
+  // offset -- would otherwise be computed ahead of the item's tile loop and spill across it)
+  const uint32_t ln = TileStage::fresh(lane);
+  const bool h2 = (ln & 32) != 0, h1 = (ln & 16) != 0, h0 = (ln & 8) != 0;
+  // (ds_bpermute on byte addresses formed from ln: __shfl_xor takes the lane id anew, hoisted too)
+  const auto xch = [&](float v, uint32_t bit) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((int)((ln ^ bit) << 2), __builtin_bit_cast(int, v)));
+  };
+#pragma unroll
+  for (int t = 0; t < 16; ++t) {   // lane ^ 32: k = 0, 1 stay in the lower half, k = 2, 3 in the upper
+    const float lo = fmaf(rs, kSynthShift, acc[t >> 3][t & 7]), hi = fmaf(rs, kSynthShift, acc[2 + (t >> 3)][t & 7]);
+    a[t] = (h2 ? hi : lo) + xch(h2 ? lo : hi, 32u);
+  }
+#pragma unroll
+  for (int t = 0; t < 8; ++t)      // lane ^ 16: the chunk of the pair
+    b[t] = (h1 ? a[8 + t] : a[t]) + xch(h1 ? a[t] : a[8 + t], 16u);
+#pragma unroll
+  for (int t = 0; t < 4; ++t)      // lane ^ 8: the half of the chunk
+    q[t] = (h0 ? b[4 + t] : b[t]) + xch(h0 ? b[t] : b[4 + t], 8u);
+  const float sr = wave_sum_dpp(acc_r), sl = wave_sum_dpp(acc_loss), sw = wave_sum_dpp(acc_w);
+  {
+    const uint32_t g = ln >> 3, cc = ln & (LPR - 1);
+    *reinterpret_cast<float4_*>(dst + (8 * (cc + ((g >> 1) & 3) * LPR) + 4 * (g & 1))) = q;
+  }
+  if (ln == 0) {
+    dst[DP] = sr;
+    dst[DP + 1] = sl;
+    dst[DP + 2] = sw;
+  }
+  zero(acc);
+  rs = acc_r = acc_loss = acc_w = 0.f;
+}
+
+// The staged pass (glm_grad_staged_kernel: same tiles, slots, MFMA dot and waits) with
+// persistent waves: ONE launch covers every whole tile of the pass, cut into `items` row
+// items (glm_items.h), and each wave claims item after item from a ticket until none is left.
+// What the sliced launches pay per block -- 32 coefficient loads, the fragment image, a
+// first DMA batch with nothing to cover it, the LDS reduction, a slab read-modify-write, and
+// the wait of a block's fast waves for its slowest -- is paid once per wave and pass, and the
+// balancing that the 32-blocks-per-CU grid bought from the dispatcher comes from the ticket.
+// Items, not blocks, are claimed, and the loop has no block barrier (the one __syncthreads()
+// stands behind the fragment image): a wave that finds no item exits alone.
+// Inside an item the wave interleaves its nr resident and nl lineage tiles by Bresenham as
+// the staged kernel does; the tiles of a role are consecutive, so "next tile" is one tile on.
+// Result: the wave ends an item by writing the item's sums to slab row i (item_flush) and
+// zeroing its accumulators.  Every slab row is written once, in full, by whichever wave took
+// the item, from that item's rows alone in a fixed order, so the pass's result is a function
+// of (n_res, n_lin, items) only: not of the grid, nor of which wave ran what or when.
+// Next item: the wave claims it just before it takes the item's LAST resident tile (an item
+// of lineage tiles alone: after its last tile), so it holds no unstarted item for longer than
+// one tile pair and the tail of the pass is at most one item per wave.  take_tile then
+// issues the next item's first batch in place of "none after the last", and the item's last
+// take_label the next item's first label: in steady state the stager never drains.  Only an
+// item that follows one without tiles of that role starts its batch / label cold.
+// Waits: the claim's value is used at once, so the compiler puts a vmcnt(0) behind the
+// atomic.  It stands directly in front of take_tile's own wait for the batch in flight, which
+// it drains a little early together with at most one label: one vmcnt(0) per item where the
+// wave waits for its batch anyway, plus the atomic's round trip while the other waves of the
+// SIMD issue.  The hand-counted waits of TileStage stay sufficient.  vmcnt(k) returns once at
+// most k vector-memory operations are outstanding, and the loads (DMAs included) retire in
+// order among themselves.  The claim is retired where it is issued.  The flush's stores are
+// the only operations a TileStage wait does not know of: one that is older than the batch or
+// label waited for does not change which loads may remain, and one that is still outstanding
+// takes one of the k places, so fewer loads may remain than the count allows -- the wait
+// retires more than it must, never less.
+template <int LOSS, bool SMP>
+__global__ __launch_bounds__(kBlock, 3) void glm_grad_persist_kernel(
+    const uint16_t* __restrict__ X, int64_t n_res, const float* __restrict__ y, const float* __restrict__ y_lin,
+    const float* __restrict__ coef, const float* __restrict__ bptr, uint32_t seed, int64_t row0, int64_t n_lin,
+    float* __restrict__ islab, int pstride, int64_t res_row0, const int64_t* __restrict__ t_dev, uint32_t sseed,
+    uint32_t sthr, uint32_t* __restrict__ ticket, uint32_t items, double inv_items) {
+  constexpr int LPR = TileStage::LPR, CPL = TileStage::CPL, UNROLL = TileStage::UNROLL, G = TileStage::G;
+  constexpr int RT = G * UNROLL;
+  constexpr int64_t ld = kStgLd;
+  __shared__ __attribute__((aligned(256))) unsigned char slots[kWavesPerBlock * kStgWaveBytes];
+  __shared__ __attribute__((aligned(256))) unsigned char frags[kStgFragBytes];
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  const int g = lane / LPR, c = lane % LPR;
+  const float intercept = *bptr;
+  const uint32_t skey = SMP ? sample_key(sseed, (uint32_t)((t_dev ? t_dev[0] : 0) + 1)) : 0u;
+  const RowSampler smp_res{skey, sthr, res_row0}, smp_lin{skey, sthr, row0};
+
+  float w[CPL][8], acc[CPL][8];
+  float wshift = 0.f;
+#pragma unroll
+  for (int k = 0; k < CPL; ++k)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      w[k][j] = coef[8 * (c + k * LPR) + j];
+      wshift += w[k][j];
+      acc[k][j] = 0.f;
+    }
+  wshift *= kSynthShift;
+  float rs = 0.f;
+  float acc_r = 0.f, acc_loss = 0.f, acc_w = 0.f;
+
+  const uint32_t Tr = (uint32_t)(n_res / RT), Tl = (uint32_t)(n_lin / RT);
+  using lds_byte = __attribute__((address_space(3))) unsigned char;
+  build_coef_frags(frags, coef);
+  __syncthreads();   // (ahead of the first DMA: a barrier drains vmcnt; the only barrier of the kernel)
+  TileStage st{slots + wid * kStgWaveBytes,
+               (uint32_t)(uintptr_t)(lds_byte*)slots + wid * kStgWaveBytes,
+               (uint32_t)(uintptr_t)(lds_byte*)frags,
+               nullptr,
+               nullptr,
+               nullptr,
+               (int64_t)RT,
+               0u,
+               0u,
+               false,
+               reinterpret_cast<const unsigned char*>(X),
+               y,
+               y_lin,
+               0u,
+               0u,
+               0u,
+               0u,
+               false,
+               false};
+  uint32_t cur = claim_item(ticket, lane);
+  if (cur >= items) return;
+  GlmItem it = uniform_item(cur, Tr, Tl, items, inv_items);
+  for (;;) {
+    const uint32_t nr = it.nr, nl = it.nl, S = nr + nl;
+    int64_t br = (int64_t)it.r0 * RT, bl = (int64_t)it.l0 * RT;   // first row of the current tile of each role
+    // the item's first label and batch, unless the item before has sent them ahead
+    if (nl > 0 && !st.l_pre) {
+      st.yls = y_lin + bl;
+      st.l_ahead = nl;
+      st.issue_label(g, c);
+    }
+    if (nr > 0 && !st.r_pre) {
+      st.xs = st.x0 + br * (ld * 2);
+      st.yrs = y + br;
+      st.r_ahead = nr;
+      st.issue_tile(lane);
+    }
+    st.r_pre = st.l_pre = false;
+    st.nx_nr = st.nx_nl = 0u;
+    uint32_t nxt = items;
+    GlmItem nx{0u, 0u, 0u, 0u};
+    bool claimed = false;
+    const auto claim_next = [&]() {
+      claimed = true;
+      nxt = claim_item(ticket, lane);
+      if (nxt < items) {
+        nx = uniform_item(nxt, Tr, Tl, items, inv_items);
+        st.nx_r0 = nx.r0;
+        st.nx_nr = nx.nr;
+        st.nx_l0 = nx.l0;
+        st.nx_nl = nx.nl;
+      }
+    };
+    uint32_t rem = 0, r_left = nr;
+    for (uint32_t s = 0; s < S; ++s) {
+      // tile s of the item is a lineage tile iff floor((s + 1) nl / S) > floor(s nl / S)
+      rem += nl;
+      if (rem >= S) {
+        rem -= S;
+        grad_tile<RowsLineage, LPR, CPL, UNROLL, LOSS, SMP, true, true, true>(bl, n_lin, X, ld, CPL * LPR, y_lin, nullptr,
+                                                                              seed, row0, w, wshift, intercept, g, c,
+                                                                              smp_lin, acc, rs, acc_r, acc_loss, acc_w, &st);
+        bl += RT;
+      } else {
+        if (r_left == 1) claim_next();
+        --r_left;
+        staged_resident_tile<LOSS, SMP, true>(br, intercept, lane, smp_res, acc, acc_r, acc_loss, acc_w, &st);
+        br += RT;
+      }
+    }
+    if (!claimed) claim_next();
+    item_flush<LPR, CPL>(acc, rs, acc_r, acc_loss, acc_w, islab + (int64_t)cur * pstride, lane);
+    if (nxt >= items) break;
+    cur = nxt;
+    it = nx;
+  }
+}
+
+// Sum of the item slab, level 1: block b adds the slab rows [b kItemChunk, (b + 1) kItemChunk)
+// column by column in fp64, in row order, into mid row b.  Level 2 (glm_finish_f64_kernel)
+// adds the mid rows in a fixed order.  The chunk is a constant: the sum's order depends on the
+// number of slab rows alone.
+constexpr int kItemChunk = 256, kItemSumBlock = 320;
+__global__ __launch_bounds__(kItemSumBlock) void glm_item_sum_kernel(const float* __restrict__ slab, int64_t nrows,
+                                                                    int pstride, int ncols,
+                                                                    double* __restrict__ mid) {
+  const int64_t lo = (int64_t)blockIdx.x * kItemChunk;
+  const int64_t hi = lo + kItemChunk < nrows ? lo + kItemChunk : nrows;
+  for (int i = threadIdx.x; i < ncols; i += kItemSumBlock) {
+    double s = 0.0;
+#pragma unroll 8
+    for (int64_t r = lo; r < hi; ++r) s += (double)__builtin_nontemporal_load(slab + r * pstride + i);
+    mid[(int64_t)blockIdx.x * pstride + i] = s;
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -1531,6 +1794,26 @@ __global__ __launch_bounds__(1024) void glm_finish_kernel(const float* __restric
   }
 }
 
+// glm_finish_kernel over fp64 rows (level 2 of the item slab's sum: the mid rows of
+// glm_item_sum_kernel), same order.
+__global__ __launch_bounds__(1024) void glm_finish_f64_kernel(const double* __restrict__ mid, int nrows, int pstride,
+                                                              int ncols, double* __restrict__ out) {
+  __shared__ double red[32][33];
+  const int cx = threadIdx.x & 31, gy = threadIdx.x >> 5;
+  const int i = blockIdx.x * 32 + cx;
+  double s = 0.0;
+  if (i < ncols)
+    for (int b = gy; b < nrows; b += 32) s += mid[(int64_t)b * pstride + i];
+  red[gy][cx] = s;
+  __syncthreads();
+  if (gy == 0 && i < ncols) {
+    double t = 0.0;
+#pragma unroll 8
+    for (int q = 0; q < 32; ++q) t += red[q][cx];
+    out[i] = t;
+  }
+}
+
 // One device-side gradient-descent step on the all-reduced pass result `out`
 // (DeviceSGD): standardised coefficients bt <- bt - eta*(g/W + l2*bt), intercept
 // b <- b - eta * sum(r)/W, then refresh the fp32 kernel operand coef_eff (dpad
@@ -1698,7 +1981,93 @@ int for_row_slices(int splits, int64_t n_res, int64_t n_lin, F&& slice, int64_t 
   return 0;
 }
 
+// The persistent staged pass (glm_grad_persist_kernel): whether a pass takes it, and the item
+// slab it then needs.  persist: 0 = never; 1 = a staged-eligible pass (full_tiles, 256-column
+// bf16 rows, unweighted, `staged` as in o3s_glm_grad_mixed, taken over the whole tiles of the
+// pass) that holds both roles and has at least 64 items per resident wave -- a smaller pass
+// keeps its sliced launches, whose grid is already cut to its size; 2 = every staged-eligible
+// pass (tests).  items == 0: not taken.
+struct PersistPlan { int64_t items, slab_floats, mid_doubles; };
+// What __launch_bounds__(kBlock, 3) and 43 KB of LDS allow.  The threshold of persist == 1 is
+// formed from this constant, not from the occupancy the launch queries per instantiation, so
+// that whether a pass takes the kernel (o3s_glm_persist_plan) does not depend on loss or sampler.
+constexpr int kPersistBlocksPerCu = 3;
+constexpr int kMaxDevices = 64;
+int current_device() {
+  int dev = 0;
+  return hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < kMaxDevices ? dev : -1;
+}
+int device_cus() {
+  static int cus[kMaxDevices] = {};
+  const int dev = current_device();
+  if (dev < 0) return 256;
+  if (cus[dev] == 0) {
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) n = 256;
+    cus[dev] = n;
+  }
+  return cus[dev];
+}
+PersistPlan persist_plan(int64_t ld, int64_t n_res, int64_t n_lin, bool weighted, int full_tiles, int staged,
+                         int persist, int item_tiles, int pstride) {
+  constexpr int64_t RT = TileStage::G * TileStage::UNROLL;
+  const PersistPlan none{0, 0, 0};
+  if (persist <= 0 || item_tiles <= 0 || !full_tiles || ld != kStgLd || weighted || n_res < 0 || n_lin < 0) return none;
+  const uint64_t Tr = (uint64_t)(n_res / RT), Tl = (uint64_t)(n_lin / RT);
+  if (Tr + Tl == 0 || Tr >= kGlmItemMaxTiles || Tl >= kGlmItemMaxTiles) return none;
+  if (!(staged >= 2 || (staged == 1 && Tr > 0 && Tl > 0))) return none;
+  const uint64_t items = glm_item_count(Tr, Tl, (uint64_t)item_tiles);
+  if (items > kGlmItemMaxTiles) return none;
+  if (persist == 1) {
+    const uint64_t waves = (uint64_t)kPersistBlocksPerCu * device_cus() * kWavesPerBlock;
+    if (Tr == 0 || Tl == 0 || items < 64 * waves) return none;
+  }
+  const int64_t rows = (int64_t)items + 1;   // the last row is the ragged rows' launch's
+  return PersistPlan{(int64_t)items, rows * pstride, (rows + kItemChunk - 1) / kItemChunk * pstride};
+}
+template <int LOSS, bool SMP>
+int persist_blocks_per_cu() {   // cached per device and instantiation
+  static int occ[kMaxDevices] = {};
+  const int dev = current_device();
+  if (dev < 0) return 1;
+  if (occ[dev] == 0) {
+    int o = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, glm_grad_persist_kernel<LOSS, SMP>, kBlock, 0) != hipSuccess ||
+        o < 1)
+      o = 1;
+    occ[dev] = o;
+  }
+  return occ[dev];
+}
+// out[0..ncols) = the column sums of slab rows 0 .. nrows - 1, in fp64, in an order that
+// depends on nrows alone (two levels: glm_item_sum_kernel, glm_finish_f64_kernel).
+int launch_item_finish(const float* islab, int64_t nrows, int pstride, int ncols, double* imid, double* out,
+                       hipStream_t st) {
+  const int chunks = (int)((nrows + kItemChunk - 1) / kItemChunk);
+  hipLaunchKernelGGL(glm_item_sum_kernel, dim3(chunks), dim3(kItemSumBlock), 0, st, islab, nrows, pstride, ncols, imid);
+  O3S_CHECK_LAUNCH();
+  hipLaunchKernelGGL(glm_finish_f64_kernel, dim3((ncols + 31) / 32), dim3(1024), 0, st, imid, chunks, pstride, ncols,
+                     out);
+  O3S_CHECK_LAUNCH();
+  return 0;
+}
+
 }  // namespace
+
+// What o3s_glm_grad_mixed with the same arguments needs for the persistent staged pass: the
+// number of items (0: the pass does not take it) and the sizes of the item slab (floats) and
+// of its fp64 mid rows.
+O3S_API int o3s_glm_persist_plan(int64_t ld, int64_t n_res, int64_t n_lin, int weighted, int full_tiles, int staged,
+                                 int persist, int item_tiles, int64_t* items, int64_t* slab_floats,
+                                 int64_t* mid_doubles) {
+  Layout l;
+  if (!resolve_layout(ld, &l)) return -1;
+  const PersistPlan p = persist_plan(ld, n_res, n_lin, weighted != 0, full_tiles, staged, persist, item_tiles, l.dpad + 4);
+  *items = p.items;
+  *slab_floats = p.slab_floats;
+  *mid_doubles = p.mid_doubles;
+  return 0;
+}
 
 // Number of fp32 slots per partial-slab row and the padded width for `ld`.
 O3S_API int o3s_glm_layout(int64_t ld, int* dpad, int* pstride) {
@@ -1762,21 +2131,38 @@ O3S_API int o3s_glm_grad(int loss, int src, const void* X, int64_t ld, int64_t n
 // staged: 1 = the whole-tile slices of an unweighted pass over the 8x4 layout
 // (256-column rows) that hold rows of both roles run through glm_grad_staged_kernel; 2 = those
 // of one role alone too; every other case, and 0, takes the kernels above.
+// persist / item_tiles: see persist_plan.  A pass that takes the persistent kernel runs all its
+// whole tiles in ONE launch of min(blocks that fit the card, items / 4) blocks -- `grid` and
+// `splits` do not shape it -- whose waves claim items from *ticket (zeroed here, on st); item i
+// goes to row i of islab, the ragged rows' launch to row `items`, and the two-level finish
+// sums those rows through imid into out.  Such a pass neither reads nor writes `partial`.
+// persist_blocks > 0 caps that launch's blocks (tests: one block takes its four waves through
+// every item; the result does not depend on it).
+// Returns -2, and launches nothing, when islab / imid are smaller than o3s_glm_persist_plan
+// says or the ticket is missing.
 O3S_API int o3s_glm_grad_mixed(int loss, const void* X, int64_t ld, int64_t n_res, const float* y,
                                const float* sw, const float* coef, uint32_t seed, int64_t row0,
                                int64_t n_lin, float* partial, int grid, double* out, int waves,
                                int64_t res_row0, const int64_t* t_dev, uint32_t sseed,
-                               uint32_t sthr, int splits, int full_tiles, int staged, hipStream_t st) {
+                               uint32_t sthr, int splits, int full_tiles, int staged, int persist, int item_tiles,
+                               float* islab, int64_t islab_floats, double* imid, int64_t imid_doubles,
+                               uint32_t* ticket, int persist_blocks, hipStream_t st) {
   Layout l;
   if (!resolve_layout(ld, &l) || grid <= 0 || n_res < 0 || n_lin < 0) return -1;
   const int pstride = l.dpad + 4;
+  const PersistPlan plan = persist_plan(ld, n_res, n_lin, sw != nullptr, full_tiles, staged, persist, item_tiles, pstride);
+  if (plan.items > 0 && (!islab || !imid || !ticket || islab_floats < plan.slab_floats ||
+                         imid_doubles < plan.mid_doubles))
+    return -2;
+  bool persisted = false;
   const uint16_t* Xh = (const uint16_t*)X;
   const bool smp = sthr < (1u << 24);
   const int rc = with_remapped_layout_and_loss(l, loss, [&](auto L, auto C, auto LOSS) {
     constexpr int U = C >= 8 ? 1 : 8 / C;
     constexpr int64_t RT = (kWave / L) * U;
     // rows [r_lo, r_lo + r_n) of X and lineage rows [l_lo, l_lo + l_n) in one launch
-    auto slice = [&](auto FULL, int g, int64_t r_lo, int64_t r_n, int64_t l_lo, int64_t l_n, int pacc) {
+    auto slice = [&](auto FULL, int g, int64_t r_lo, int64_t r_n, int64_t l_lo, int64_t l_n, int pacc,
+                     float* partial) {
       // the mask-free kernel reads whole tiles unguarded: never launch it on anything else
       if (FULL && (r_n % RT != 0 || l_n % RT != 0 || ld != 8 * L * C)) return -1;
       const float* y_lin = y + n_res + l_lo;
@@ -1813,25 +2199,53 @@ O3S_API int o3s_glm_grad_mixed(int loss, const void* X, int64_t ld, int64_t n_re
     // where its masked twin does not)
     constexpr bool kHasFull = !(L >= 32 && C == 4);
     const int64_t r_full = n_res / RT * RT, l_full = n_lin / RT * RT;
+    if constexpr (L == TileStage::LPR && C == TileStage::CPL) {
+      if (plan.items > 0) {
+        // every whole tile of the pass in one launch of persistent waves
+        persisted = true;
+        if (hipMemsetAsync(ticket, 0, sizeof(uint32_t), st) != hipSuccess) return -3;
+        auto go_persist = [&](auto SMP) {
+          int64_t fit = (int64_t)persist_blocks_per_cu<LOSS, SMP>() * device_cus();
+          if (persist_blocks > 0 && persist_blocks < fit) fit = persist_blocks;
+          const int64_t need = (plan.items + kWavesPerBlock - 1) / kWavesPerBlock;
+          launch(glm_grad_persist_kernel<LOSS, SMP>, (int)(fit < need ? fit : need), st, Xh, r_full, y, y + n_res, coef,
+                 coef + l.dpad, seed, row0, l_full, islab, pstride, res_row0, t_dev, sseed, sthr, ticket,
+                 (uint32_t)plan.items, glm_item_inv((uint64_t)plan.items));
+        };
+        if (smp) go_persist(std::true_type{});
+        else go_persist(std::false_type{});
+        O3S_CHECK_LAUNCH();
+        int64_t rows = plan.items;
+        if (r_full != n_res || l_full != n_lin) {
+          // the ragged rows: one block of the masked kernel, which writes slab row `items` in full
+          const int rc2 = slice(std::false_type{}, 1, r_full, n_res - r_full, l_full, n_lin - l_full, 0,
+                                islab + plan.items * pstride);
+          O3S_CHECK_LAUNCH();
+          if (rc2 != 0) return rc2;
+          ++rows;
+        }
+        return launch_item_finish(islab, rows, pstride, l.dpad + 3, imid, out, st);
+      }
+    }
     if constexpr (kHasFull) {
       if (full_tiles && ld == 8 * L * C && r_full + l_full > 0) {
         const int rc = for_row_slices(
             splits, n_res, n_lin,
             [&](int64_t r_lo, int64_t r_n, int64_t l_lo, int64_t l_n, int pacc) {
-              return slice(std::true_type{}, grid, r_lo, r_n, l_lo, l_n, pacc);
+              return slice(std::true_type{}, grid, r_lo, r_n, l_lo, l_n, pacc, partial);
             },
             RT);
         if (rc != 0 || (r_full == n_res && l_full == n_lin)) return rc;
-        const int rc2 = slice(std::false_type{}, 1, r_full, n_res - r_full, l_full, n_lin - l_full, 1);
+        const int rc2 = slice(std::false_type{}, 1, r_full, n_res - r_full, l_full, n_lin - l_full, 1, partial);
         O3S_CHECK_LAUNCH();
         return rc2;
       }
     }
     return for_row_slices(splits, n_res, n_lin, [&](int64_t r_lo, int64_t r_n, int64_t l_lo, int64_t l_n, int pacc) {
-      return slice(std::false_type{}, grid, r_lo, r_n, l_lo, l_n, pacc);
+      return slice(std::false_type{}, grid, r_lo, r_n, l_lo, l_n, pacc, partial);
     });
   });
-  if (rc != 0) return rc;
+  if (rc != 0 || persisted) return rc;
   return launch_finish(partial, grid, pstride, l.dpad + 3, out, 0, st);
 }
 

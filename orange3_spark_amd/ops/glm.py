@@ -10,6 +10,8 @@ Loss ids match the kernel: 0 logistic (y in {0,1}), 1 hinge (y in {0,1}, LinearS
 """
 from __future__ import annotations
 
+import ctypes
+import logging
 import os
 
 import numpy as np
@@ -18,6 +20,7 @@ import torch
 from . import _native as N
 
 LOSS_LOGISTIC, LOSS_HINGE, LOSS_SQUARED = 0, 1, 2
+log = logging.getLogger(__name__)
 _MASK = 0xFFFFFFFF
 
 
@@ -189,6 +192,44 @@ class GlmWorkspace:
         self.grid = grid or (N.num_cus(self.device) * 8 if self.device.type == "cuda" else 1)
         self.partial = torch.empty(self.grid * self.pstride, dtype=torch.float32, device=self.device)
         self.out = torch.empty(self.dpad + 3, dtype=torch.float64, device=self.device)
+        # the persistent staged pass (MIX_PERSIST): its item slab and the slab's fp64 mid rows,
+        # grown on demand (reserve_items), and the ticket its waves claim items from
+        self.islab = self.imid = self.ticket = None
+        self.persist_failed = False     # the slab did not fit: this workspace keeps the sliced launches
+
+    def item_slab(self, slab_floats: int, mid_doubles: int) -> None:
+        """Make the item slab hold at least this much (it only grows)."""
+        if self.ticket is None:
+            self.ticket = torch.zeros(1, dtype=torch.int32, device=self.device)
+        if self.islab is None or self.islab.numel() < slab_floats:
+            self.islab = None
+            self.islab = torch.empty(slab_floats, dtype=torch.float32, device=self.device)
+        if self.imid is None or self.imid.numel() < mid_doubles:
+            self.imid = None
+            self.imid = torch.empty(mid_doubles, dtype=torch.float64, device=self.device)
+
+    def reserve_items(self, n_res: int, n_lin: int, weighted: bool) -> int:
+        """The ``MIX_PERSIST`` to run a mixed pass over these rows with: ``MIX_PERSIST`` itself, with
+        the item slab the pass needs in place (``o3s_glm_persist_plan``; 4 KB per item of
+        ``MIX_ITEM_TILES`` tile pairs, 254 MB for 1B rows at the default), or 0 -- the sliced
+        launches -- when that slab does not fit the card beside the table.  A fit calls this when
+        it sets its workspace up, so the memory is found, or found missing, before the first pass."""
+        if MIX_PERSIST <= 0 or self.persist_failed or self.device.type != "cuda":
+            return 0
+        items, slab, mid = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        N.check(N.kernels().o3s_glm_persist_plan(self.ld, n_res, n_lin, int(weighted), MIX_FULL_TILES, MIX_STAGED,
+                                                 MIX_PERSIST, MIX_ITEM_TILES, ctypes.byref(items), ctypes.byref(slab),
+                                                 ctypes.byref(mid)), "glm_persist_plan")
+        if items.value > 0:
+            try:
+                self.item_slab(slab.value, mid.value)
+            except torch.cuda.OutOfMemoryError:
+                self.islab = self.imid = None
+                self.persist_failed = True
+                log.warning("GLM item slab of %.0f MB (O3S_GLM_MIX_ITEM_TILES=%d) does not fit; "
+                            "the pass keeps its sliced launches", slab.value * 4 / 2 ** 20, MIX_ITEM_TILES)
+                return 0
+        return MIX_PERSIST
 
 
 _ROWS_MSG = ("GPU GLM pass expects a contiguous bf16 feature matrix (or a contiguous fp32 one whose row "
@@ -272,6 +313,16 @@ MIX_FULL_TILES = int(os.environ.get("O3S_GLM_MIX_FULL", "1"))
 # passes over one role alone too (3-5 % slower than unstaged; for tests); 0, and every other
 # layout, weighted fits and MIX_FULL_TILES = 0: the unstaged kernels
 MIX_STAGED = int(os.environ.get("O3S_GLM_MIX_STAGED", "1"))
+# the staged pass as ONE launch of persistent waves that claim row items from a ticket
+# (csrc/glm.hip glm_grad_persist_kernel, csrc/glm_items.h): 1 = staged passes that hold both
+# roles and have at least 64 items per resident wave (smaller ones keep the sliced launches);
+# 2 = every staged pass (tests); 0 = the sliced launches, bit for bit what they were
+MIX_PERSIST = int(os.environ.get("O3S_GLM_MIX_PERSIST", "1"))
+# whole tiles (16 rows each) of both roles per item of that pass; the result depends on it
+MIX_ITEM_TILES = int(os.environ.get("O3S_GLM_MIX_ITEM_TILES", "256"))
+# cap on the blocks of that launch (0: as many as fit the card); the result does not depend on
+# it -- tests use 1 to take four waves through every item
+MIX_PERSIST_BLOCKS = int(os.environ.get("O3S_GLM_MIX_PERSIST_BLOCKS", "0"))
 
 
 def mix_splits(n_rows: int) -> int:
@@ -340,11 +391,17 @@ def glm_grad_mixed(X: torch.Tensor, y: torch.Tensor, sw: torch.Tensor | None, n_
                                              mix_splits(nr), N.stream_of(X)), "glm_grad_f32")
         return ws.out
     cf = _coef_buf(coef, ws.dpad, ws.device, intercept=intercept)
-    N.check(N.kernels().o3s_glm_grad_mixed(loss, X.data_ptr(), ld, nr, y.data_ptr(), N.ptr(sw),
-                                           cf.data_ptr(), seed & _MASK, row0, n_lin, ws.partial.data_ptr(),
-                                           ws.grid, ws.out.data_ptr(), MIX_WAVES, int(res_row0),
-                                           N.ptr(t_dev), int(sample_seed) & _MASK, thr, mix_splits(nr + n_lin),
-                                           MIX_FULL_TILES, MIX_STAGED, N.stream_of(X)),
+    lib = N.kernels()
+    persist = ws.reserve_items(nr, n_lin, sw is not None)
+    has = ws.islab is not None
+    N.check(lib.o3s_glm_grad_mixed(loss, X.data_ptr(), ld, nr, y.data_ptr(), N.ptr(sw),
+                                   cf.data_ptr(), seed & _MASK, row0, n_lin, ws.partial.data_ptr(),
+                                   ws.grid, ws.out.data_ptr(), MIX_WAVES, int(res_row0),
+                                   N.ptr(t_dev), int(sample_seed) & _MASK, thr, mix_splits(nr + n_lin),
+                                   MIX_FULL_TILES, MIX_STAGED, persist, MIX_ITEM_TILES,
+                                   N.ptr(ws.islab), ws.islab.numel() if has else 0,
+                                   N.ptr(ws.imid), ws.imid.numel() if has else 0, N.ptr(ws.ticket),
+                                   MIX_PERSIST_BLOCKS, N.stream_of(X)),
             "glm_grad_mixed")
     return ws.out
 
