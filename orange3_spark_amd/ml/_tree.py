@@ -9,6 +9,7 @@ from ..runtime.tracing import trace
 
 from ..frame import column as C
 from ..models import trees as TR
+from ..ops import tree_predict as TP
 from . import common as U
 from .base import Estimator, Model
 from .linalg import DenseVector, SparseVector
@@ -167,8 +168,14 @@ class _TreeModelMixin:
         out = super()._transform(df)
         lc = self.getOrDefault(self.leafCol) if self.hasParam("leafCol") and self.isDefined(self.leafCol) else ""
         if lc:                                  # Spark leafCol: per-tree preorder leaf indices
-            X = self._X(df)
-            out = out.withColumnData(lc, U.vec_out(torch.stack([t.leaf_index(X) for t in self._ens.trees], 1)))
+            X = self._rows(df)
+            p = self._packed_for(X)
+            if p is not None:                   # one LEAF-mode pass over the stored rows
+                leaves = TP.ensemble_predict(X, X.shape[1], p, TP.LEAF)
+            else:
+                X = self._as_walked(X)
+                leaves = torch.stack([t.leaf_index(X) for t in self._ens.trees], 1)
+            out = out.withColumnData(lc, U.vec_out(leaves))
         return out
 
     @property
@@ -201,6 +208,66 @@ class _TreeModelMixin:
     def _X(self, df):
         X = U.dense_features(df, self.getOrDefault(self.featuresCol))
         return X.float() if X.is_cuda else X.to(torch.float64)
+
+    @staticmethod
+    def _as_walked(X):
+        """Rows as the per-tree torch walk takes them (fp32 on the GPU, fp64 on the host)."""
+        return X.float() if X.is_cuda else X.to(torch.float64)
+
+    def _rows(self, df):
+        """The rows to score.  A plain resident vector column whose stored matrix the scoring
+        kernel takes is handed over as stored (bf16 or fp32, its row stride kept: a view of
+        the logical columns, no fp32 copy); everything else as :meth:`_X` gives it."""
+        from ..frame.spill import SpilledVectorColumn
+        from ..synthetic import LineageVectorColumn
+        c = U.features_column(df, self.getOrDefault(self.featuresCol))
+        if isinstance(c, C.VectorColumn) and not isinstance(c, (LineageVectorColumn, SpilledVectorColumn)):
+            X = c.dense()
+            if self._packed_for(X) is not None:
+                return X
+        return self._X(df)
+
+    def _packed_for(self, X):
+        """The packed ensemble for scoring the rows ``X`` with the kernel, or None: the
+        per-tree torch walk scores them (CPU rows, the switch, the gate, a tree that does not
+        validate).  Packed tables are built at the first use and kept per LDS split; they
+        belong to this object and its current ensemble only (never pickled, saved or copied)."""
+        ens = self._ens
+        if not (TP.fused_enabled() and isinstance(X, torch.Tensor) and X.is_cuda and X.dim() == 2 and ens.trees):
+            return None
+        cache = self.__dict__.get("_tp_cache")
+        if cache is None or cache[0] is not ens or cache[1] != len(ens.trees):
+            cache = self.__dict__["_tp_cache"] = (ens, len(ens.trees), {})
+        packs = cache[2]
+        if "tree_bytes" not in packs:
+            try:
+                packs["tree_bytes"] = 8 * max(TP.tree_node_count(t) for t in ens.trees)
+            except (IndexError, ValueError):
+                packs["tree_bytes"] = None
+        tree_bytes = packs["tree_bytes"]
+        d = X.shape[1]
+        V = ens.num_classes if (ens.kind != "gbt" and ens.num_classes) else 1
+        if tree_bytes is None or d < self.numFeatures or not TP.predict_kernel_ok(X, d, V, tree_bytes):
+            return None
+        budget = TP.node_budget(X, d, tree_bytes)
+        if budget not in packs:
+            try:
+                packs[budget] = TP.pack_ensemble(ens.trees, ens.weights, ens.kind, ens.num_classes, budget,
+                                                 self.numFeatures or None)
+            except TP.PackError:
+                packs[budget] = None
+        return packs[budget]
+
+    def _ensemble_sum(self, X):
+        """fp64 [n, V] sum over the trees of weight * leaf value (V = 1) or of the leaf class
+        distributions, by the scoring kernel; None where the torch walk has to do it."""
+        p = self._packed_for(X)
+        return None if p is None else TP.ensemble_predict(X, X.shape[1], p, TP.SUM)
+
+    def __getstate__(self):
+        st = dict(self.__dict__)
+        st.pop("_tp_cache", None)
+        return st
 
     # persistence, Spark's layouts: ensembles (RF / GBT) write data/ = (treeID, nodeData)
     # rows + treesMetadata/ = (treeID, metadata JSON, weights); a single decision tree
@@ -385,10 +452,16 @@ class _TreeClassifierModel(_TreeModelMixin, U.ProbabilisticClassifierMixin, Mode
         self._ens = TR.Ensemble([], [], "rf", 2)
 
     def _features_for_predict(self, df, name):
-        return self._X(df)
+        return self._rows(df)
 
     def _raw(self, X):
         ens = self._ens
+        S = self._ensemble_sum(X)
+        if S is not None:
+            if ens.kind == "gbt":
+                return torch.stack([-S[:, 0], S[:, 0]], 1)
+            return S
+        X = self._as_walked(X) if X.dtype == torch.bfloat16 else X
         if ens.kind == "gbt":
             F = sum(w * t.predict_value(X)[:, 0] for t, w in zip(ens.trees, ens.weights))
             return torch.stack([-F, F], 1)
@@ -422,9 +495,15 @@ class _TreeRegressorModel(_TreeModelMixin, U.PredictionModelMixin, Model, MLWrit
         super().__init__()
         self._ens = TR.Ensemble([], [], "rf", 0)
 
+    def _features_for_predict(self, df, name):
+        return self._rows(df)
+
     def _predict_tensor(self, X):
-        X = X.float() if X.is_cuda else X.to(torch.float64)
         ens = self._ens
+        S = self._ensemble_sum(X)
+        if S is not None:
+            return S[:, 0] / len(ens.trees) if ens.kind == "rf" else S[:, 0]
+        X = X.float() if X.is_cuda else X.to(torch.float64)
         vals = [w * t.predict_value(X)[:, 0] for t, w in zip(ens.trees, ens.weights)]
         s = sum(vals)
         return s / len(vals) if ens.kind == "rf" else s

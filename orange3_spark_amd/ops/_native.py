@@ -117,6 +117,9 @@ _SIGS: dict[str, list] = {
     "o3s_gram": [c_vp, c_i32, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp],
     "o3s_gmm_layout": [c_i32, c_i32, C.POINTER(c_i32), C.POINTER(c_i32), C.POINTER(c_i64), C.POINTER(c_i32)],
     "o3s_gmm_estep": [c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp],
+    "o3s_tree_predict_layout": [c_i64, c_i32, c_i32, c_i32, C.POINTER(c_i32), C.POINTER(c_i32)],
+    "o3s_tree_predict": [c_vp, c_i32, c_i64, c_i64, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_i32,
+                         c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp],
 }
 
 
@@ -188,7 +191,7 @@ def host():
 
 
 PRELOAD_TAGS = ("glm", "trees", "kmeans", "als", "als_dense", "als_exact", "assemble", "binsum", "eval",
-                "sampling", "sparse", "text", "probe", "gram", "gmm")
+                "sampling", "sparse", "text", "probe", "gram", "gmm", "tree_predict")
 
 
 def preload(tags=PRELOAD_TAGS) -> dict:
