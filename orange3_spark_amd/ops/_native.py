@@ -190,8 +190,9 @@ def host():
     return _HOST
 
 
-PRELOAD_TAGS = ("glm", "trees", "kmeans", "als", "als_dense", "als_exact", "assemble", "binsum", "eval",
-                "sampling", "sparse", "text", "probe", "gram", "gmm", "tree_predict")
+PRELOAD_TAGS = ("glm_grad", "glm_mixed", "glm_stats", "glm_softmax", "trees", "kmeans", "als", "als_dense",
+                "als_exact", "assemble", "binsum", "eval", "sampling", "sparse", "text", "probe", "gram", "gmm",
+                "tree_predict")
 
 
 def preload(tags=PRELOAD_TAGS) -> dict:

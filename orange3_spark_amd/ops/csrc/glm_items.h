@@ -1,4 +1,4 @@
-// Row items of the persistent staged GLM pass (glm_grad_persist_kernel in glm.hip).
+// Row items of the persistent staged GLM pass (glm_grad_persist_kernel in glm_mixed.hip).
 //
 // A pass over Tr resident and Tl lineage whole tiles is cut into I = ceil((Tr + Tl) / T)
 // items.  Item i holds the resident tiles [floor(i Tr / I), floor((i + 1) Tr / I)) and the

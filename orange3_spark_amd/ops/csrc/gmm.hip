@@ -8,7 +8,7 @@
 // component k) and lse [n].  Every output is a function of its own row only: no slabs, no
 // atomics, the same bits for any grid.
 //
-// The product is the forward half of the multinomial pass (glm.hip) with the K d whitened
+// The product is the forward half of the multinomial pass (glm_softmax.hip) with the K d whitened
 // coordinates as classes, on v_mfma_f32_32x32x16_bf16 with A = a block of W (lane (r, h):
 // coordinate 32 cb + r, dims 16 s + 8 h .. + 8) and B = the rows (lane (r, h): row r, the same
 // dims), so a lane's 16 accumulators are 16 coordinates of ONE data row and |z|^2 is an

@@ -5,7 +5,7 @@
 // GeneralizedLinearRegression (ops/gram.py::weighted_gram).  Rows are the GLM layout: bf16
 // [n, ld] or fp32 [n, ld], ld % 8 == 0, logical width d <= 256.
 //
-// A Gram matrix is the backward half of the multinomial pass (glm.hip, R^T X) with R := X:
+// A Gram matrix is the backward half of the multinomial pass (glm_softmax.hip, R^T X) with R := X:
 // every row is shifted and scaled to z = sqrt(w) (x - shift), and the augmented row
 // [z | 0 .. | sqrt(w) y | sqrt(w)] of DA = 32 NBA columns (NBA = ceil((d + 2) / 32) <= 9; the
 // y and ones columns are the last two) is multiplied with itself, so those columns deliver

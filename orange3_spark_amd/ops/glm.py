@@ -1,7 +1,7 @@
 """GLM streaming ops: fused gradient/loss pass, margins, synthetic row generation.
 
 GPU tensors -- bf16 rows, or fp32 rows whose stride is a multiple of 8 (:func:`kernel_rows`)
--- dispatch to ``csrc/glm.hip``; CPU tensors use the PyTorch reference
+-- dispatch to ``csrc/glm_*.hip``; CPU tensors use the PyTorch reference
 implementations below (fp64 math), which also serve as the numerics oracle in the
 tests (kernel vs plain fp32/fp64 PyTorch of the same op).
 
@@ -76,7 +76,7 @@ def row_keys(seed: int, rows: torch.Tensor) -> torch.Tensor:
 
 
 def _mix24(h: torch.Tensor) -> torch.Tensor:
-    """Torch twin of csrc/glm.hip ``mix24`` (bijective; v_mad_u32_u24 steps + xorshifts)."""
+    """Torch twin of csrc/glm_rows.h ``mix24`` (bijective; v_mad_u32_u24 steps + xorshifts)."""
     h = h ^ (h >> 16)
     h = ((h & 0xFFFFFF) * 0xED5AD4 + h) & _MASK
     h = h ^ (h >> 15)
@@ -84,7 +84,7 @@ def _mix24(h: torch.Tensor) -> torch.Tensor:
 
 
 def feat_keys(seed: int, rows: torch.Tensor) -> torch.Tensor:
-    """Per-row feature keys (csrc/glm.hip ``feat_key``); labels use :func:`row_keys`."""
+    """Per-row feature keys (csrc/glm_rows.h ``feat_key``); labels use :func:`row_keys`."""
     lo = rows & _MASK
     hi = rows >> 32
     k = _mix24((lo + ((seed * 0x9E3779B1) & _MASK)) & _MASK)
@@ -95,7 +95,7 @@ def synth_features_torch(fk: torch.Tensor, ld: int, d: int) -> torch.Tensor:
     """bf16 [n, ld] features for feature keys ``fk`` (int64 [n], :func:`feat_keys`).
 
     Word i = mix24(fk + i*0x9E3779) gives features 4i..4i+3 (byte q -> column 4i+q) as
-    (2b - 255)/256: 256 symmetric levels in (-1, 1), exact in bf16 (csrc/glm.hip
+    (2b - 255)/256: 256 symmetric levels in (-1, 1), exact in bf16 (csrc/glm_rows.h
     ``synth_chunk``).  All ``ld`` columns are generated (synthetic widths are rounded up to
     a multiple of 8; the ground-truth weights of columns >= d are zero, so those are pure
     noise features).
@@ -300,21 +300,21 @@ MIX_WAVES = int(os.environ.get("O3S_GLM_MIX_WAVES", "3"))
 # waves/SIMD the masked fused summarizer kernel is compiled for (2: no spill, 3: 6-VGPR spill;
 # its mask-free form fits 3 without a spill either way)
 STATS_WAVES = int(os.environ.get("O3S_GLM_STATS_WAVES", "2"))
-# rows per launch slice of a mixed pass (csrc/glm.hip o3s_glm_grad_mixed ``splits``): long
+# rows per launch slice of a mixed pass (csrc/glm_mixed.hip o3s_glm_grad_mixed ``splits``): long
 # passes restart their grid-stride walk every this many rows, at most 16 slices
 MIX_SLICE_ROWS = int(os.environ.get("O3S_GLM_MIX_SLICE_ROWS", str(64 << 20)))
 # whole tiles of a mixed pass (gradient and summarizer) through the mask-free kernel, the
-# ragged rows in a launch of their own (csrc/glm.hip o3s_glm_grad_mixed / o3s_glm_stats_mixed
+# ragged rows in a launch of their own (csrc/glm_mixed.hip o3s_glm_grad_mixed / o3s_glm_stats_mixed
 # ``full_tiles``); 0: the masked kernel throughout
 MIX_FULL_TILES = int(os.environ.get("O3S_GLM_MIX_FULL", "1"))
 # whole tiles of an unweighted gradient pass over 256-column bf16 rows through the
-# kernel that stages each wave's next resident tile in LDS (csrc/glm.hip
+# kernel that stages each wave's next resident tile in LDS (csrc/glm_mixed.hip
 # glm_grad_staged_kernel): 1 = passes that hold resident and lineage rows (where it gains), 2 =
 # passes over one role alone too (3-5 % slower than unstaged; for tests); 0, and every other
 # layout, weighted fits and MIX_FULL_TILES = 0: the unstaged kernels
 MIX_STAGED = int(os.environ.get("O3S_GLM_MIX_STAGED", "1"))
 # the staged pass as ONE launch of persistent waves that claim row items from a ticket
-# (csrc/glm.hip glm_grad_persist_kernel, csrc/glm_items.h): 1 = staged passes that hold both
+# (csrc/glm_mixed.hip glm_grad_persist_kernel, csrc/glm_items.h): 1 = staged passes that hold both
 # roles and have at least 64 items per resident wave (smaller ones keep the sliced launches);
 # 2 = every staged pass (tests); 0 = the sliced launches, bit for bit what they were
 MIX_PERSIST = int(os.environ.get("O3S_GLM_MIX_PERSIST", "1"))
@@ -338,7 +338,7 @@ def sample_threshold(fraction: float) -> int:
 
 
 def sample_key(seed: int, it: int) -> int:
-    """Torch/host twin of csrc/glm.hip ``sample_key`` (per-iteration sampling key)."""
+    """Torch/host twin of csrc/glm_rows.h ``sample_key`` (per-iteration sampling key)."""
     t = torch.tensor([(int(it) * 0x9E3779B1 + 0x7F4A7C15) & _MASK], dtype=torch.int64)
     return int(_fmix32((int(seed) & _MASK) ^ _fmix32(t))[0])
 
@@ -357,7 +357,7 @@ def glm_grad_mixed(X: torch.Tensor, y: torch.Tensor, sw: torch.Tensor | None, n_
                    ws: GlmWorkspace, res_row0: int = 0, t_dev: torch.Tensor | None = None,
                    sample_seed: int = 0, fraction: float = 1.0) -> torch.Tensor:
     """Resident rows of ``X`` plus ``n_lin`` lineage rows (global rows ``row0..``) in ONE
-    launch (csrc/glm.hip ``glm_grad_mixed_kernel``): memory-bound and VALU-bound tiles
+    launch (csrc/glm_mixed.hip ``glm_grad_mixed_kernel``): memory-bound and VALU-bound tiles
     are interleaved inside every wave so both resources stay busy.  ``y``/``sw`` are the
     materialised label/weight columns of all ``X.shape[0] + n_lin`` rows.  Overwrites
     ``ws.out``.
@@ -408,7 +408,7 @@ def glm_grad_mixed(X: torch.Tensor, y: torch.Tensor, sw: torch.Tensor | None, n_
 
 def glm_stats_mixed(X: torch.Tensor, y: torch.Tensor, sw: torch.Tensor | None, n_lin: int, d: int,
                     seed: int, row0: int, grid: int | None = None) -> torch.Tensor | None:
-    """Summarizer pass fused with the first gradient (csrc/glm.hip ``glm_stats_mixed_kernel``)
+    """Summarizer pass fused with the first gradient (csrc/glm_stats.hip ``glm_stats_mixed_kernel``)
     over the resident rows of ``X`` and ``n_lin`` lineage rows: fp64 [s1 (dpad) | s2 (dpad) |
     syx (dpad) | sum w | sum w y | sum w y^2] with s1 = sum w x, s2 = sum w x^2, syx =
     sum w y x.  Returns None when the layout has no fused instantiation (ld > 2048)."""
@@ -515,7 +515,7 @@ def softmax_kernel_ok(X: torch.Tensor, K: int) -> bool:
 
 def softmax_pass(X: torch.Tensor, y: torch.Tensor, sw: torch.Tensor | None, W: torch.Tensor, b: torch.Tensor):
     """One fused multinomial pass over the rows of X (``glm_softmax_kernel`` for bf16 rows,
-    ``glm_softmax_f32_kernel`` for fp32 rows, csrc/glm.hip).
+    ``glm_softmax_f32_kernel`` for fp32 rows, csrc/glm_softmax.hip).
 
     X bf16 or fp32 [n, d] (row stride a multiple of 8), y int32 labels, sw fp32 weights or
     None, W fp32 [K, d] effective coefficients, b fp32 [K].  Returns fp64 (G [K, d] = sum_i

@@ -1,4 +1,4 @@
-"""fp32 feature rows through the fused GLM kernels (csrc/glm.hip, the ``*_f32`` kernels) vs
+"""fp32 feature rows through the fused GLM kernels (csrc/glm_mixed.hip and csrc/glm_stats.hip, the ``*_f32`` kernels) vs
 fp64 PyTorch references.
 
 The inputs are deliberately NOT representable in bf16 (normal values around 10), and the

@@ -1,4 +1,4 @@
-"""Numerics of the fused GLM kernels (csrc/glm.hip) vs plain PyTorch fp64 references."""
+"""Numerics of the fused GLM kernels (csrc/glm_*.hip) vs plain PyTorch fp64 references."""
 import pytest
 import torch
 

@@ -1,4 +1,4 @@
-"""Every row layout of the fused GLM kernels (csrc/glm.hip), in both element types.
+"""Every row layout of the fused GLM kernels (csrc/glm_*.hip), in both element types.
 
 A row of ld = 8 * nch columns is split over LPR lanes with CPL 16-B (bf16) / 32-B (fp32)
 chunks each.  The mixed, stats and fp32 passes use the nine "remapped" (LPR, CPL) layouts,

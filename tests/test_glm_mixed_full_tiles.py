@@ -1,5 +1,5 @@
 """The mixed GLM pass split on the host into whole tiles (mask-free kernel) and the ragged
-rest (one launch of the masked kernel that adds into slab row 0): csrc/glm.hip
+rest (one launch of the masked kernel that adds into slab row 0): csrc/glm_mixed.hip
 ``o3s_glm_grad_mixed`` with ``full_tiles``, switched by ``ops.glm.MIX_FULL_TILES``.
 
 Shapes: d = 256 is the 8x4 layout (tile = 16 rows); d = 32 the 4x1 layout (tile = 128 rows).

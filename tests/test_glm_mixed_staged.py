@@ -1,5 +1,5 @@
 """The mixed GLM gradient pass with the resident tiles staged through a per-wave LDS slot
-(csrc/glm.hip ``glm_grad_staged_kernel``, switched by ``ops.glm.MIX_STAGED``): whole tiles of
+(csrc/glm_mixed.hip ``glm_grad_staged_kernel``, switched by ``ops.glm.MIX_STAGED``): whole tiles of
 unweighted passes over d = 256 rows (the 8x4 layout, tile = 16 rows, block = 4
 waves).  Every case checks the staged pass against fp64, against the unstaged mask-free pass
 (another fp32 block-sum order, nothing more) and against itself: a slot overwritten before it

@@ -1,4 +1,4 @@
-"""The resident tile of ``glm_grad_staged_kernel`` (csrc/glm.hip) takes its 16 dot products on
+"""The resident tile of ``glm_grad_staged_kernel`` (csrc/glm_mixed.hip) takes its 16 dot products on
 the matrix cores: the tile out of the wave's LDS slot is the B operand of
 ``v_mfma_f32_16x16x32_bf16``, the coefficients, split into bf16 hi + mid + lo terms, are rows
 0 - 2 of the A operand, and the lanes 0 - 15 finish the 16 rows.  What can go wrong there and

@@ -1,5 +1,5 @@
 """The staged GLM pass as one launch of persistent waves that claim row items from a ticket
-(csrc/glm.hip ``glm_grad_persist_kernel``, csrc/glm_items.h; ``ops.glm.MIX_PERSIST`` /
+(csrc/glm_mixed.hip ``glm_grad_persist_kernel``, csrc/glm_items.h; ``ops.glm.MIX_PERSIST`` /
 ``MIX_ITEM_TILES``).  Every case forces the path (``MIX_PERSIST = 2``) on d = 256 rows and checks
 it against fp64 (the tolerances of tests/test_glm_mixed_staged.py), against the sliced launches
 (``MIX_PERSIST = 0``: another fp32 summation order, nothing more), against itself (two
