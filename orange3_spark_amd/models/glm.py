@@ -127,8 +127,15 @@ class GlmData:
             self.ws = G.GlmWorkspace(self.device, self.ld,
                                      grid=int(os.environ.get("O3S_GLM_GRID_MIX", str(grid))))
             # the persistent pass's item slab, if these rows take it, now and not in the first pass
-            self.ws.reserve_items(int(self.X.shape[0]), int(self.lineage[2] if self.lineage else 0),
-                                  self.sw is not None)
+            nl = int(self.lineage[2] if self.lineage else 0)
+            self.ws.reserve_items(int(self.X.shape[0]), nl, self.sw is not None)
+            # a pass that will persist reads its 0/1 labels from bit planes packed here, once per
+            # fit (one host sync for the flag; the planes live on the workspace, so a captured
+            # step replays with the same addresses).  The float column stays: the summarizer,
+            # the ragged rows and every other pass read it.
+            if (self.ws.persist_items > 0 and self.sw is None and self.spill is None and G.MIX_LABEL_BITS
+                    and self.y.shape[0] == int(self.X.shape[0]) + nl):
+                self.ws.pack_labels(self.y, int(self.X.shape[0]), nl)
         elif self.kernel and self.lineage and self.X.shape[0] and os.environ.get("O3S_GLM_OVERLAP", "1") == "1":
             cus = N.num_cus(self.device)
             res_grid = int(os.environ.get("O3S_GLM_GRID_RES", str(cus * 8)))

@@ -32,7 +32,8 @@ _SIGS: dict[str, list] = {
                      c_vp, c_f32, c_vp, c_i32, c_vp, c_i32, c_vp],
     "o3s_glm_grad_mixed": [c_i32, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_u32, c_i64, c_i64,
                            c_vp, c_i32, c_vp, c_i32, c_i64, c_vp, c_u32, c_u32, c_i32, c_i32, c_i32, c_i32, c_i32,
-                           c_vp, c_i64, c_vp, c_i64, c_vp, c_i32, c_vp],
+                           c_vp, c_i64, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_vp],
+    "o3s_glm_pack_labels": [c_vp, c_i64, c_vp, c_vp, c_vp],
     "o3s_glm_persist_plan": [c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, C.POINTER(c_i64),
                              C.POINTER(c_i64), C.POINTER(c_i64)],
     "o3s_glm_stats_mixed": [c_vp, c_i64, c_i64, c_vp, c_vp, c_u32, c_i64, c_i64, c_vp, c_i32, c_vp, c_i32, c_i32,

@@ -17,6 +17,9 @@
 // A pass large enough runs that kernel's tiles as ONE launch of persistent waves that claim row
 // items from a ticket (glm_grad_persist_kernel, glm_items.h), which fills the wave slots that
 // the blocks of 14 sliced launches left empty between their prologues and epilogues.
+// That launch reads the 0/1 labels of a logistic or hinge pass from two bit planes packed once
+// per fit (o3s_glm_pack_labels, glm_grad_persist_kernel<.., YB = true>): 125 MB instead of the
+// 4 GB float column per pass at 1B rows, fetched with scalar loads instead of label DMAs.
 //
 // Every kernel of this file is register-tuned to the instruction: the notes in them record
 // what moving a statement into a helper cost in scratch or occupancy.  Device code here
@@ -91,6 +94,15 @@ struct TileStage {
   const float* yl0;
   uint32_t nx_r0, nx_nr, nx_l0, nx_nl;
   bool r_pre, l_pre;
+  // glm_grad_persist_kernel<.., YB = true> only (zero and unused elsewhere): the labels as bits.
+  // br0 / bl0: the two bit planes read as dwords (tile t of a role: bits 16 (t & 1) .. + 15 of
+  // dword t >> 1); rt / lt: the next tile of each role whose word is to be loaded; rw / lw: the
+  // dword that holds the labels of the role's next tile to be TAKEN, and rsh / lsh = 16 (t & 1)
+  // of that tile (the shift is applied where the word is used, never where it is loaded: a use
+  // makes the compiler wait for the load).  All wave-uniform: the loads are scalar loads.
+  const uint32_t* br0;
+  const uint32_t* bl0;
+  uint32_t rt, lt, rw, lw, rsh, lsh;
 
   // (an empty asm per use: otherwise the offsets are hoisted out of the loop as invariants)
   __device__ static __forceinline__ uint32_t fresh(int v) {
@@ -100,11 +112,14 @@ struct TileStage {
   // the tile row whose label lane (g, c) takes: RowReduce<8, 2>::base(c) * G + g
   __device__ static __forceinline__ uint32_t label_off(uint32_t g, uint32_t c) { return ((c >> 2) * G + g) * 4; }
 
+  // YB: no label DMA (a batch is 8 operations); the tile's label word is a scalar load.
+  template <bool YB = false>
   __device__ __forceinline__ void issue_tile(int lane) {
     const uint32_t ln = fresh(lane);
     // (a resident tile's rows are finished in the lanes 0 .. 15, row = lane: TileStage::dot)
-    __builtin_amdgcn_global_load_lds(reinterpret_cast<const unsigned char*>(yrs) + (ln & 15) * 4,
-                                     slot + kStgTileBytes, 4, 0, 0);
+    if constexpr (!YB)
+      __builtin_amdgcn_global_load_lds(reinterpret_cast<const unsigned char*>(yrs) + (ln & 15) * 4,
+                                       slot + kStgTileBytes, 4, 0, 0);
     // lane (g, c') = (ln >> 3, ln & 7) fetches chunk c' ^ t(g) of row g (+ 8u, + 8k chunks)
     const uint32_t xoff = (ln >> 3) * (kStgLd * 2) + ((ln ^ (ln >> 4)) & 7) * 16;
 #pragma unroll
@@ -114,9 +129,23 @@ struct TileStage {
         __builtin_amdgcn_global_load_lds(xs + (u * G * kStgLd * 2 + k * LPR * 16) + xoff, slot + (u * CPL + k) * 1024,
                                          16, 0, kAuxNt);
     xs += tstep * (kStgLd * 2);
-    yrs += tstep;
+    if constexpr (YB) {
+      rw = br0[rt >> 1];
+      rsh = (rt & 1u) << 4;
+      ++rt;
+    } else {
+      yrs += tstep;
+    }
     --r_ahead;
     lab_younger = false;
+  }
+  // YB: the label word of the next lineage tile (lt) of the item; l_ahead counts the item's
+  // lineage tiles whose word is not loaded yet.
+  __device__ __forceinline__ void issue_bits() {
+    lw = bl0[lt >> 1];
+    lsh = (lt & 1u) << 4;
+    ++lt;
+    --l_ahead;
   }
   __device__ __forceinline__ void issue_label(int g, int c) {
     __builtin_amdgcn_global_load_lds(reinterpret_cast<const unsigned char*>(yls) + label_off(fresh(g), fresh(c)),
@@ -132,15 +161,50 @@ struct TileStage {
   // X^T r layout; yv: the label of tile row lane & 15; fa: the coefficient fragments (A
   // operand, see dot) of the k-steps 0 - 2.
   // PERSIST: after the last tile of the item the stager moves on to the next item's first.
-  template <bool PERSIST = false>
+  // YB: the batch is the only thing in flight (vmcnt(0)); the slot holds no label, yv comes
+  // from the tile's label word (rw), which was loaded with the batch and is valid behind the
+  // closing lgkmcnt(0) of the reads (the compiler, which knows of the scalar load, puts its own
+  // wait in front of the use as well); only then is the next tile's word loaded over it.
+  template <bool PERSIST = false, bool YB = false>
   __device__ __forceinline__ void take_tile(int lane, short8 (&xb)[8], short8 (&xv)[UNROLL][CPL], float& yv,
                                             short8 (&fa)[3]) {
-    if (lab_younger) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
+    if constexpr (YB) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    else if (lab_younger) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     const uint32_t ln = fresh(lane);
     // operand read: image (R >> 3) * 4 + q, row R & 7, position s ^ t(R), t(R) = (R >> 1) & 3;
     // sbase is a multiple of 128, so the xor acts on the position bits alone
     const uint32_t b0 = sbase + ((ln & 8) << 9) + ((ln >> 4) << 10) + ((ln & 7) << 7) + (((ln >> 1) & 3) << 4);
+    if constexpr (YB) {
+      asm volatile(
+          "ds_read_b128 %16, %24\n\t"
+          "ds_read_b128 %17, %24 offset:1024\n\t"
+          "ds_read_b128 %18, %24 offset:2048\n\t"
+          "ds_read_b128 %0, %19\n\t"
+          "ds_read_b128 %1, %20\n\t"
+          "ds_read_b128 %2, %21\n\t"
+          "ds_read_b128 %3, %22\n\t"
+          "ds_read_b128 %4, %19 offset:64\n\t"
+          "ds_read_b128 %5, %20 offset:64\n\t"
+          "ds_read_b128 %6, %21 offset:64\n\t"
+          "ds_read_b128 %7, %22 offset:64\n\t"
+          "ds_read_b128 %8, %23\n\t"
+          "ds_read_b128 %9, %23 offset:1024\n\t"
+          "ds_read_b128 %10, %23 offset:2048\n\t"
+          "ds_read_b128 %11, %23 offset:3072\n\t"
+          "ds_read_b128 %12, %23 offset:4096\n\t"
+          "ds_read_b128 %13, %23 offset:5120\n\t"
+          "ds_read_b128 %14, %23 offset:6144\n\t"
+          "ds_read_b128 %15, %23 offset:7168\n\t"
+          "s_waitcnt lgkmcnt(0)"
+          : "=&v"(xb[0]), "=&v"(xb[1]), "=&v"(xb[2]), "=&v"(xb[3]), "=&v"(xb[4]), "=&v"(xb[5]), "=&v"(xb[6]),
+            "=&v"(xb[7]), "=&v"(xv[0][0]), "=&v"(xv[0][1]), "=&v"(xv[0][2]), "=&v"(xv[0][3]), "=&v"(xv[1][0]),
+            "=&v"(xv[1][1]), "=&v"(xv[1][2]), "=&v"(xv[1][3]), "=&v"(fa[0]), "=&v"(fa[1]), "=&v"(fa[2])
+          : "v"(b0), "v"(b0 ^ 16u), "v"(b0 ^ 32u), "v"(b0 ^ 48u), "v"(sbase + ((ln ^ (ln >> 4)) << 4)),
+            "v"(fbase + ln * 16)
+          : "memory");
+      yv = (float)(((rw >> rsh) >> (ln & 15u)) & 1u);
+    } else
     asm volatile(
         "ds_read_b128 %17, %26\n\t"
         "ds_read_b128 %18, %26 offset:1024\n\t"
@@ -172,13 +236,14 @@ struct TileStage {
     if constexpr (PERSIST) {
       if (r_ahead == 0 && nx_nr > 0) {
         xs = x0 + (uint64_t)nx_r0 * (UNROLL * G * kStgLd * 2);
-        yrs = yr0 + (uint64_t)nx_r0 * (UNROLL * G);
+        if constexpr (YB) rt = nx_r0;
+        else yrs = yr0 + (uint64_t)nx_r0 * (UNROLL * G);
         r_ahead = nx_nr;
         nx_nr = 0;
         r_pre = true;
       }
     }
-    if (r_ahead > 0) issue_tile(lane);
+    if (r_ahead > 0) issue_tile<YB>(lane);
     __builtin_amdgcn_sched_barrier(0);   // the DMAs go out ahead of the tile's math
   }
   // The 16 rows' dot products with the coefficients on the matrix cores: D (16 x 16) = A x B
@@ -250,6 +315,13 @@ struct TileStage {
     }
     if (l_ahead > 0) issue_label(g, c);
   }
+  // YB: the lineage tile's label out of its word (lw, loaded a lineage tile earlier or, for an
+  // item's first, at the end of the item before: glm_grad_persist_kernel): no vector-memory
+  // wait and no LDS read.  Then the word of the item's next lineage tile, if it has one.
+  __device__ __forceinline__ void take_bits(int g, int c, float& yv) {
+    yv = (float)(((lw >> lsh) >> (label_off(fresh(g), fresh(c)) >> 2)) & 1u);
+    if (l_ahead > 0) issue_bits();
+  }
 };
 static_assert(kStgTileBytes == 8192 && kStgLabelBytes == 256, "the asm offsets in TileStage");
 
@@ -260,7 +332,7 @@ static_assert(kStgTileBytes == 8192 && kStgLabelBytes == 256, "the asm offsets i
 // STAGED (with FULL, unweighted, lineage rows): the labels come out of the wave's LDS slot
 // (stg); y and sw are not read here.  (The staged resident tile is staged_resident_tile.)
 template <class SRC, int LPR, int CPL, int UNROLL, int LOSS, bool SMP, bool FULL = false, bool STAGED = false,
-          bool PERSIST = false>
+          bool PERSIST = false, bool YB = false>
 __device__ __forceinline__ void grad_tile(
     int64_t base, int64_t n, const typename SRC::elem* __restrict__ X, int64_t ld, int nch,
     const float* __restrict__ y, const float* __restrict__ sw, uint32_t seed, int64_t row0, const float (&w)[CPL][8],
@@ -339,7 +411,8 @@ __device__ __forceinline__ void grad_tile(
   constexpr bool kDpp = LPR == 8 && UNROLL == 2;
   if constexpr (kDpp) row_reduce_8x2(dot, c);
   else RR::run(dot, c);
-  if constexpr (STAGED && SRC::kLineage) stg->template take_label<PERSIST>(g, c, yy[0]);   // as late as the label is needed
+  if constexpr (STAGED && SRC::kLineage && YB) stg->take_bits(g, c, yy[0]);
+  else if constexpr (STAGED && SRC::kLineage) stg->template take_label<PERSIST>(g, c, yy[0]);   // as late as the label is needed
   if constexpr (STAGED && SMP) {   // (and the sampler's hash: a register less across the dot products)
     // (the lane's row in the tile made opaque: hipcc otherwise keeps grow0 + it, 64 bits per
     // role, in registers across the loop, which spills)
@@ -382,7 +455,7 @@ __device__ __forceinline__ void grad_tile(
 // add nowhere): margin = (lo + mid) + hi partial dots, one loss_terms for the 16 rows, no
 // cross-lane reduction.  Lane (g, c) then fetches the residuals of its rows g and 8 + g from
 // the lanes g and 8 + g.  base: the tile's first row within the role (the sampler's row index).
-template <int LOSS, bool SMP, bool PERSIST = false>
+template <int LOSS, bool SMP, bool PERSIST = false, bool YB = false>
 __device__ __forceinline__ void staged_resident_tile(int64_t base, float intercept, int lane, const RowSampler smp,
                                                      float (&acc)[TileStage::CPL][8], float& acc_r, float& acc_loss,
                                                      float& acc_w, TileStage* stg) {
@@ -390,7 +463,7 @@ __device__ __forceinline__ void staged_resident_tile(int64_t base, float interce
   short8 xb[8], xv[UNROLL][CPL];
   float yv;
   short8 fa[3];
-  stg->template take_tile<PERSIST>(lane, xb, xv, yv, fa);
+  stg->template take_tile<PERSIST, YB>(lane, xb, xv, yv, fa);
   const float4_ d = stg->dot(lane, xb, fa);
   float wv = 1.f;
   if constexpr (SMP) {
@@ -630,6 +703,12 @@ __global__ __launch_bounds__(kBlock, 3) void glm_grad_staged_kernel(
   grad_epilogue<LPR, CPL>(acc, acc_r, acc_loss, acc_w, partial, pstride, pacc, lane, wid, c);
 }
 
+// The float label column of a persistent pass, or none when its labels are bit planes (YB).
+template <bool YB, class T>
+__device__ __forceinline__ const float* label_col(const T* p) {
+  if constexpr (YB) return nullptr;
+  else return p;
+}
 // One lane takes the next ticket (a vector atomic with return); every lane gets its value.
 __device__ __forceinline__ uint32_t claim_item(uint32_t* __restrict__ ticket, int lane) {
   uint32_t t = 0;
@@ -722,9 +801,31 @@ __device__ __forceinline__ void item_flush(float (&acc)[CPL][8], float& rs, floa
 // label waited for does not change which loads may remain, and one that is still outstanding
 // takes one of the k places, so fewer loads may remain than the count allows -- the wait
 // retires more than it must, never less.
-template <int LOSS, bool SMP>
+// YB (labels from bit planes; YB = false is the kernel as it was, instruction for instruction):
+// y / y_lin are the two planes of o3s_glm_pack_labels read as dwords, and a tile's 16 labels are
+// one wave-uniform word, fetched by a scalar load (TileStage::issue_tile<true>, issue_bits): no
+// label DMA, no label ds_read_b32, no lab_younger.  A batch is 8 operations, at most one batch
+// is in flight, take_tile waits vmcnt(0) and the lineage tile has no vmcnt wait at all; the
+// claim's atomic and the flush's stores remain the only other vector-memory operations, and the
+// argument above carries over.  A resident tile's word is loaded with its batch (so across an
+// item boundary too), a lineage tile's one lineage tile ahead, and the first lineage word of
+// the next item at the end of the item, once that item is known, ahead of the flush.  Only
+// loads are scalar: nothing scalar is ever written to memory.
+// lgkmcnt with a scalar load outstanding: scalar loads count in lgkmcnt and may return out of
+// order relative to LDS operations, so (1) a scalar result is valid only behind lgkmcnt(0), and
+// (2) a counted wait sees one more operation.  (1): the words are plain C++ loads, so the
+// compiler, which knows of them, puts its own lgkmcnt(0) in front of each first use, and the
+// resident tile's use also stands behind take_tile's closing lgkmcnt(0); no use is moved in
+// front of either.  (2): the counted waits of TileStage::dot (lgkmcnt(2), (1)) stay sufficient
+// for the LDS reads: LDS operations retire in order among themselves, and an outstanding scalar
+// load only takes a place in the count, so fewer LDS reads may remain than the count allows.
+// The slot keeps its two 256-B label areas (43 008 B per block): TileStage's offsets are shared
+// with glm_grad_staged_kernel.  loss_terms gets the same expression on the same values, so the
+// outputs are bit-equal to YB = false (tests/test_glm_label_bits.py).
+template <int LOSS, bool SMP, bool YB = false>
 __global__ __launch_bounds__(kBlock, 3) void glm_grad_persist_kernel(
-    const uint16_t* __restrict__ X, int64_t n_res, const float* __restrict__ y, const float* __restrict__ y_lin,
+    const uint16_t* __restrict__ X, int64_t n_res, const std::conditional_t<YB, uint32_t, float>* __restrict__ y,
+    const std::conditional_t<YB, uint32_t, float>* __restrict__ y_lin,
     const float* __restrict__ coef, const float* __restrict__ bptr, uint32_t seed, int64_t row0, int64_t n_lin,
     float* __restrict__ islab, int pstride, int64_t res_row0, const int64_t* __restrict__ t_dev, uint32_t sseed,
     uint32_t sthr, uint32_t* __restrict__ ticket, uint32_t items, double inv_items) {
@@ -769,31 +870,47 @@ __global__ __launch_bounds__(kBlock, 3) void glm_grad_persist_kernel(
                0u,
                false,
                reinterpret_cast<const unsigned char*>(X),
-               y,
-               y_lin,
+               label_col<YB>(y),
+               label_col<YB>(y_lin),
                0u,
                0u,
                0u,
                0u,
                false,
                false};
+  if constexpr (YB) {
+    st.br0 = y;
+    st.bl0 = y_lin;
+  }
   uint32_t cur = claim_item(ticket, lane);
   if (cur >= items) return;
   GlmItem it = uniform_item(cur, Tr, Tl, items, inv_items);
+  if constexpr (YB) {
+    // the label word of the wave's very first lineage tile; every later item's comes at the end
+    // of the item before it
+    if (it.nl > 0) {
+      st.lt = it.l0;
+      st.l_ahead = it.nl;
+      st.issue_bits();
+    }
+  }
   for (;;) {
     const uint32_t nr = it.nr, nl = it.nl, S = nr + nl;
     int64_t br = (int64_t)it.r0 * RT, bl = (int64_t)it.l0 * RT;   // first row of the current tile of each role
     // the item's first label and batch, unless the item before has sent them ahead
-    if (nl > 0 && !st.l_pre) {
-      st.yls = y_lin + bl;
-      st.l_ahead = nl;
-      st.issue_label(g, c);
+    if constexpr (!YB) {
+      if (nl > 0 && !st.l_pre) {
+        st.yls = y_lin + bl;
+        st.l_ahead = nl;
+        st.issue_label(g, c);
+      }
     }
     if (nr > 0 && !st.r_pre) {
       st.xs = st.x0 + br * (ld * 2);
-      st.yrs = y + br;
+      if constexpr (YB) st.rt = it.r0;
+      else st.yrs = y + br;
       st.r_ahead = nr;
-      st.issue_tile(lane);
+      st.template issue_tile<YB>(lane);
     }
     st.r_pre = st.l_pre = false;
     st.nx_nr = st.nx_nl = 0u;
@@ -817,18 +934,27 @@ __global__ __launch_bounds__(kBlock, 3) void glm_grad_persist_kernel(
       rem += nl;
       if (rem >= S) {
         rem -= S;
-        grad_tile<RowsLineage, LPR, CPL, UNROLL, LOSS, SMP, true, true, true>(bl, n_lin, X, ld, CPL * LPR, y_lin, nullptr,
-                                                                              seed, row0, w, wshift, intercept, g, c,
-                                                                              smp_lin, acc, rs, acc_r, acc_loss, acc_w, &st);
+        grad_tile<RowsLineage, LPR, CPL, UNROLL, LOSS, SMP, true, true, true, YB>(bl, n_lin, X, ld, CPL * LPR, label_col<YB>(y_lin),
+                                                                                  nullptr, seed, row0, w, wshift, intercept, g, c,
+                                                                                  smp_lin, acc, rs, acc_r, acc_loss, acc_w, &st);
         bl += RT;
       } else {
         if (r_left == 1) claim_next();
         --r_left;
-        staged_resident_tile<LOSS, SMP, true>(br, intercept, lane, smp_res, acc, acc_r, acc_loss, acc_w, &st);
+        staged_resident_tile<LOSS, SMP, true, YB>(br, intercept, lane, smp_res, acc, acc_r, acc_loss, acc_w, &st);
         br += RT;
       }
     }
     if (!claimed) claim_next();
+    if constexpr (YB) {
+      // the next item is known and this item's lineage tiles are all taken: its first lineage
+      // word goes out now, ahead of the flush
+      if (nxt < items && nx.nl > 0) {
+        st.lt = nx.l0;
+        st.l_ahead = nx.nl;
+        st.issue_bits();
+      }
+    }
     item_flush<LPR, CPL>(acc, rs, acc_r, acc_loss, acc_w, islab + (int64_t)cur * pstride, lane);
     if (nxt >= items) break;
     cur = nxt;
@@ -898,14 +1024,14 @@ PersistPlan persist_plan(int64_t ld, int64_t n_res, int64_t n_lin, bool weighted
   const int64_t rows = (int64_t)items + 1;   // the last row is the ragged rows' launch's
   return PersistPlan{(int64_t)items, rows * pstride, (rows + kItemChunk - 1) / kItemChunk * pstride};
 }
-template <int LOSS, bool SMP>
+template <int LOSS, bool SMP, bool YB = false>
 int persist_blocks_per_cu() {   // cached per device and instantiation
   static int occ[kMaxDevices] = {};
   const int dev = current_device();
   if (dev < 0) return 1;
   if (occ[dev] == 0) {
     int o = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, glm_grad_persist_kernel<LOSS, SMP>, kBlock, 0) != hipSuccess ||
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, glm_grad_persist_kernel<LOSS, SMP, YB>, kBlock, 0) != hipSuccess ||
         o < 1)
       o = 1;
     occ[dev] = o;
@@ -925,7 +1051,44 @@ int launch_item_finish(const float* islab, int64_t nrows, int pstride, int ncols
   return 0;
 }
 
+// The 0/1 labels of a role as a bit plane: word t (16 bits) holds the rows 16 t .. 16 t + 15,
+// bit j is row 16 t + j.  One lane per row, the wave's 64 bits by ballot, the lanes 0, 16, 32
+// and 48 store one word each; n16 is a multiple of 16, so a wave holds whole words only.
+// *flag is set when a label is neither 0.0f nor 1.0f by its bit pattern (NaN, -0.0, 0.5 ...).
+constexpr int kPackBlock = 256;
+__global__ __launch_bounds__(kPackBlock) void glm_pack_labels_kernel(const float* __restrict__ y, int64_t n16,
+                                                                    uint16_t* __restrict__ bits, int* __restrict__ flag) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t step = (int64_t)gridDim.x * kPackBlock;
+  // (n16 rounded up to whole waves: every lane of a wave takes part in each ballot)
+  const int64_t end = (n16 + kWave - 1) / kWave * kWave;
+  bool bad = false;
+  for (int64_t i = (int64_t)blockIdx.x * kPackBlock + threadIdx.x; i < end; i += step) {
+    const bool in = i < n16;
+    const uint32_t u = in ? __float_as_uint(y[i]) : 0u;
+    bad |= u != 0u && u != 0x3f800000u;
+    const unsigned long long m = __ballot(u == 0x3f800000u);
+    if ((lane & 15) == 0 && in) bits[i >> 4] = (uint16_t)(m >> lane);
+  }
+  if (__ballot(bad) != 0ull && lane == 0) atomicOr(flag, 1);
+}
+
 }  // namespace
+
+// bits[t] (t < n / 16) = the labels y[16 t .. 16 t + 15] as one bit each (bit j: row 16 t + j);
+// only the n / 16 whole tiles are packed.  *flag (a device int the caller has zeroed) is set
+// non-zero when one of those labels is neither 0.0f nor 1.0f, compared as bit patterns.
+O3S_API int o3s_glm_pack_labels(const float* y, int64_t n, uint16_t* bits, int* flag, hipStream_t st) {
+  if (n < 0 || !flag || (n >= 16 && (!y || !bits))) return -1;
+  const int64_t n16 = n / 16 * 16;
+  if (n16 == 0) return 0;
+  const int64_t need = (n16 + kPackBlock - 1) / kPackBlock;
+  const int64_t cap = (int64_t)device_cus() * 32;
+  hipLaunchKernelGGL(glm_pack_labels_kernel, dim3((unsigned)(need < cap ? need : cap)), dim3(kPackBlock), 0, st, y, n16,
+                     bits, flag);
+  O3S_CHECK_LAUNCH();
+  return 0;
+}
 
 // What o3s_glm_grad_mixed with the same arguments needs for the persistent staged pass: the
 // number of items (0: the pass does not take it) and the sizes of the item slab (floats) and
@@ -964,6 +1127,11 @@ O3S_API int o3s_glm_persist_plan(int64_t ld, int64_t n_res, int64_t n_lin, int w
 // sums those rows through imid into out.  Such a pass neither reads nor writes `partial`.
 // persist_blocks > 0 caps that launch's blocks (tests: one block takes its four waves through
 // every item; the result does not depend on it).
+// bits_res / bits_lin: the 0/1 labels of the resident and of the lineage rows as bit planes
+// (o3s_glm_pack_labels over y, n_res and over y + n_res, n_lin; each 4-byte aligned with at
+// least one dword behind its last word), or null.  With both given, a logistic or hinge pass
+// that takes the persistent kernel reads its whole tiles' labels from them
+// (glm_grad_persist_kernel<.., YB = true>); the ragged rows' launch and every other pass read y.
 // Returns -2, and launches nothing, when islab / imid are smaller than o3s_glm_persist_plan
 // says or the ticket is missing.
 O3S_API int o3s_glm_grad_mixed(int loss, const void* X, int64_t ld, int64_t n_res, const float* y,
@@ -972,7 +1140,8 @@ O3S_API int o3s_glm_grad_mixed(int loss, const void* X, int64_t ld, int64_t n_re
                                int64_t res_row0, const int64_t* t_dev, uint32_t sseed,
                                uint32_t sthr, int splits, int full_tiles, int staged, int persist, int item_tiles,
                                float* islab, int64_t islab_floats, double* imid, int64_t imid_doubles,
-                               uint32_t* ticket, int persist_blocks, hipStream_t st) {
+                               uint32_t* ticket, int persist_blocks, const uint32_t* bits_res,
+                               const uint32_t* bits_lin, hipStream_t st) {
   Layout l;
   if (!resolve_layout(ld, &l) || grid <= 0 || n_res < 0 || n_lin < 0) return -1;
   const int pstride = l.dpad + 4;
@@ -1027,9 +1196,19 @@ O3S_API int o3s_glm_grad_mixed(int loss, const void* X, int64_t ld, int64_t n_re
         persisted = true;
         if (hipMemsetAsync(ticket, 0, sizeof(uint32_t), st) != hipSuccess) return -3;
         with_bool(smp, [&](auto SMP) {
+          const int64_t need = (plan.items + kWavesPerBlock - 1) / kWavesPerBlock;
+          if constexpr (decltype(LOSS)::value != LOSS_SQUARED) {
+            if (bits_res && bits_lin) {
+              int64_t fit = (int64_t)persist_blocks_per_cu<LOSS, SMP, true>() * device_cus();
+              if (persist_blocks > 0 && persist_blocks < fit) fit = persist_blocks;
+              launch(glm_grad_persist_kernel<LOSS, SMP, true>, (int)(fit < need ? fit : need), st, Xh, r_full, bits_res,
+                     bits_lin, coef, coef + l.dpad, seed, row0, l_full, islab, pstride, res_row0, t_dev, sseed, sthr,
+                     ticket, (uint32_t)plan.items, glm_item_inv((uint64_t)plan.items));
+              return 0;
+            }
+          }
           int64_t fit = (int64_t)persist_blocks_per_cu<LOSS, SMP>() * device_cus();
           if (persist_blocks > 0 && persist_blocks < fit) fit = persist_blocks;
-          const int64_t need = (plan.items + kWavesPerBlock - 1) / kWavesPerBlock;
           launch(glm_grad_persist_kernel<LOSS, SMP>, (int)(fit < need ? fit : need), st, Xh, r_full, y, y + n_res, coef,
                  coef + l.dpad, seed, row0, l_full, islab, pstride, res_row0, t_dev, sseed, sthr, ticket,
                  (uint32_t)plan.items, glm_item_inv((uint64_t)plan.items));

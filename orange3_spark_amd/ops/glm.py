@@ -195,7 +195,39 @@ class GlmWorkspace:
         # the persistent staged pass (MIX_PERSIST): its item slab and the slab's fp64 mid rows,
         # grown on demand (reserve_items), and the ticket its waves claim items from
         self.islab = self.imid = self.ticket = None
+        self.persist_items = 0
         self.persist_failed = False     # the slab did not fit: this workspace keeps the sliced launches
+        # the 0/1 labels of one label column as two bit planes (pack_labels; MIX_LABEL_BITS):
+        # (resident plane, lineage plane, (y.data_ptr(), n_res, n_lin)), or None
+        self.label_bits = None
+        self.used_label_bits = False    # whether the last glm_grad_mixed on this workspace handed the planes in
+
+    def pack_labels(self, y: torch.Tensor, n_res: int, n_lin: int) -> bool:
+        """Pack the labels ``y`` (fp32, ``n_res`` resident rows then ``n_lin`` lineage rows) once, as
+        two bit planes -- one per role, because ``n_res`` need not be a multiple of 16 -- for the
+        persistent pass (csrc/glm_mixed.hip ``o3s_glm_pack_labels``).  Returns whether the planes
+        are in place: False, and none kept, when a label of a whole tile is neither 0.0 nor 1.0.
+        One host sync (the flag).  The planes are tied to ``y``'s address and the two counts; a
+        caller that changes ``y`` in place packs again.  They stay alive on the workspace, at
+        fixed addresses, so a captured step may replay the pass that reads them."""
+        self.label_bits = None
+        if self.device.type != "cuda" or y.dtype != torch.float32 or not y.is_contiguous() \
+                or y.shape[0] != n_res + n_lin:
+            return False
+        lib = N.kernels()
+        flag = torch.zeros(1, dtype=torch.int32, device=self.device)
+        planes = []
+        for off, n in ((0, n_res), (n_res, n_lin)):
+            # n // 16 words of 16 bits in whole dwords, and one zeroed dword behind them: the
+            # kernel reads the words as aligned dwords
+            plane = torch.zeros((n // 16 + 1) // 2 + 1, dtype=torch.int32, device=self.device)
+            N.check(lib.o3s_glm_pack_labels(y.data_ptr() + 4 * off, n, plane.data_ptr(), flag.data_ptr(),
+                                            N.stream_of(y)), "glm_pack_labels")
+            planes.append(plane)
+        if int(flag.item()) != 0:
+            return False
+        self.label_bits = (planes[0], planes[1], (y.data_ptr(), int(n_res), int(n_lin)))
+        return True
 
     def item_slab(self, slab_floats: int, mid_doubles: int) -> None:
         """Make the item slab hold at least this much (it only grows)."""
@@ -214,6 +246,7 @@ class GlmWorkspace:
         ``MIX_ITEM_TILES`` tile pairs, 254 MB for 1B rows at the default), or 0 -- the sliced
         launches -- when that slab does not fit the card beside the table.  A fit calls this when
         it sets its workspace up, so the memory is found, or found missing, before the first pass."""
+        self.persist_items = 0          # items of the pass just planned (0: it keeps the sliced launches)
         if MIX_PERSIST <= 0 or self.persist_failed or self.device.type != "cuda":
             return 0
         items, slab, mid = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
@@ -229,6 +262,7 @@ class GlmWorkspace:
                 log.warning("GLM item slab of %.0f MB (O3S_GLM_MIX_ITEM_TILES=%d) does not fit; "
                             "the pass keeps its sliced launches", slab.value * 4 / 2 ** 20, MIX_ITEM_TILES)
                 return 0
+        self.persist_items = items.value
         return MIX_PERSIST
 
 
@@ -323,6 +357,25 @@ MIX_ITEM_TILES = int(os.environ.get("O3S_GLM_MIX_ITEM_TILES", "256"))
 # cap on the blocks of that launch (0: as many as fit the card); the result does not depend on
 # it -- tests use 1 to take four waves through every item
 MIX_PERSIST_BLOCKS = int(os.environ.get("O3S_GLM_MIX_PERSIST_BLOCKS", "0"))
+# a logistic or hinge pass that takes the persistent kernel reads the 0/1 labels of its whole
+# tiles from two bit planes packed once per fit (GlmWorkspace.pack_labels; scalar loads in place
+# of the label DMAs, 125 MB in place of 4 GB per pass at 1B rows) when the workspace holds the
+# planes of this label column; 0 = the float column, the launches and outputs bit for bit what
+# they were.  Labels that are not all 0.0 / 1.0, squared loss, weighted fits, the ragged rows
+# and every non-persistent pass read the float column either way.
+MIX_LABEL_BITS = int(os.environ.get("O3S_GLM_MIX_LABEL_BITS", "1"))
+
+
+def pack_labels_torch(y: torch.Tensor) -> tuple[torch.Tensor, bool]:
+    """Host twin of ``o3s_glm_pack_labels``: (words, flag).  ``words`` is int32 [n // 16], word t
+    holding rows 16 t .. 16 t + 15 (bit j = row 16 t + j, values 0 .. 65535); ``flag`` is True
+    when one of the packed labels is neither 0.0 nor 1.0 by its bit pattern (NaN, -0.0, 0.5)."""
+    n16 = y.shape[0] // 16 * 16
+    u = y[:n16].detach().to("cpu", torch.float32).contiguous().view(torch.int32)
+    one = u == 0x3F800000
+    bad = bool(((u != 0) & ~one).any())
+    weights = 1 << torch.arange(16, dtype=torch.int32)
+    return (one.view(-1, 16).to(torch.int32) * weights).sum(1, dtype=torch.int32), bad
 
 
 def mix_splits(n_rows: int) -> int:
@@ -394,6 +447,12 @@ def glm_grad_mixed(X: torch.Tensor, y: torch.Tensor, sw: torch.Tensor | None, n_
     lib = N.kernels()
     persist = ws.reserve_items(nr, n_lin, sw is not None)
     has = ws.islab is not None
+    # the labels as bit planes: a persistent logistic / hinge pass over the very column packed
+    bits = ws.label_bits
+    if not (MIX_LABEL_BITS and bits is not None and ws.persist_items > 0 and sw is None
+            and loss in (LOSS_LOGISTIC, LOSS_HINGE) and bits[2] == (y.data_ptr(), nr, n_lin)):
+        bits = None
+    ws.used_label_bits = bits is not None
     N.check(lib.o3s_glm_grad_mixed(loss, X.data_ptr(), ld, nr, y.data_ptr(), N.ptr(sw),
                                    cf.data_ptr(), seed & _MASK, row0, n_lin, ws.partial.data_ptr(),
                                    ws.grid, ws.out.data_ptr(), MIX_WAVES, int(res_row0),
@@ -401,7 +460,8 @@ def glm_grad_mixed(X: torch.Tensor, y: torch.Tensor, sw: torch.Tensor | None, n_
                                    MIX_FULL_TILES, MIX_STAGED, persist, MIX_ITEM_TILES,
                                    N.ptr(ws.islab), ws.islab.numel() if has else 0,
                                    N.ptr(ws.imid), ws.imid.numel() if has else 0, N.ptr(ws.ticket),
-                                   MIX_PERSIST_BLOCKS, N.stream_of(X)),
+                                   MIX_PERSIST_BLOCKS, bits[0].data_ptr() if bits else None,
+                                   bits[1].data_ptr() if bits else None, N.stream_of(X)),
             "glm_grad_mixed")
     return ws.out
 

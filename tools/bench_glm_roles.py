@@ -4,6 +4,8 @@ after a warm-up pass.  ``--staged 0/1/2`` selects ``ops.glm.MIX_STAGED`` (reside
 through a per-wave LDS slot; 2 stages a single role too); ``--persist 0/1/2`` selects
 ``ops.glm.MIX_PERSIST`` (the ticket-scheduled persistent form of the staged pass); ``--only``
 runs one of the three, for a profiler or counter run.
+``--label-bits 0/1`` selects ``ops.glm.MIX_LABEL_BITS`` (the persistent pass reads its 0/1 labels
+from bit planes).
 ``--grid G [G ...]`` and ``--item-tiles T [T ...]`` time the mixed pass once per value on the
 same table (a static-grid sweep of the sliced launches, an item-size sweep of the persistent
 one); the per-value times are reported under ``sweep``.
@@ -40,12 +42,15 @@ def main():
     ap.add_argument("--persist", type=int, default=None)
     ap.add_argument("--grid", type=int, nargs="*", default=None)
     ap.add_argument("--item-tiles", type=int, nargs="*", default=None)
+    ap.add_argument("--label-bits", type=int, choices=[0, 1], default=None)
     ap.add_argument("--only", choices=["resident", "lineage", "mixed"], default=None)
     a = ap.parse_args()
     if a.staged is not None:
         G.MIX_STAGED = a.staged
     if a.persist is not None:
         G.MIX_PERSIST = a.persist
+    if a.label_bits is not None:
+        G.MIX_LABEL_BITS = a.label_bits
     dev = torch.device("cuda", 0)
     X, yr = G.synth_glm(a.res, a.d, seed=1, device=dev)
     ld = X.shape[1]
@@ -54,17 +59,22 @@ def main():
     grids = a.grid or [None]
     ws = G.GlmWorkspace(dev, ld, grid=grids[0])
     coef = torch.full((ld,), 0.01, device=dev)
+    if G.MIX_LABEL_BITS:
+        ws.pack_labels(y, a.res, a.lin)     # the mixed pass's label column, as a fit packs it
     roles = {
         "resident": lambda: G.glm_grad_mixed(X, yr, None, 0, a.d, 1, a.res, coef, 0.0, 0, ws),
         "lineage": lambda: G.glm_grad_mixed(X[:0], yl, None, a.lin, a.d, 1, a.res, coef, 0.0, 0, ws),
         "mixed": lambda: G.glm_grad_mixed(X, y, None, a.lin, a.d, 1, a.res, coef, 0.0, 0, ws),
     }
     out = {"res": a.res, "lin": a.lin, "d": a.d, "iters": a.iters, "staged": getattr(G, "MIX_STAGED", None),
-           "persist": getattr(G, "MIX_PERSIST", None), "grid": ws.grid, "splits": G.mix_splits(a.res + a.lin)}
+           "persist": getattr(G, "MIX_PERSIST", None), "label_bits": G.MIX_LABEL_BITS, "grid": ws.grid,
+           "splits": G.mix_splits(a.res + a.lin)}
     for name, fn in roles.items():
         if a.only and name != a.only:
             continue
         out[name + "_ms"] = _time(fn, a.iters)
+        if name == "mixed":
+            out["mixed_used_label_bits"] = ws.used_label_bits
     if len(grids) > 1 or a.item_tiles:
         sweep = []
         for grid in grids:
