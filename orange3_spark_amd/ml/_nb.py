@@ -224,6 +224,25 @@ class NaiveBayesModel(U.ProbabilisticClassifierMixin, Model, _NaiveBayesParams, 
             raw = pi - 0.5 * torch.log(2 * math.pi * var).sum(1) - 0.5 * quad
         return raw.to(torch.float64)
 
+    def _linear_spec(self):
+        mt = self.getOrDefault(self.modelType) if self.isDefined(self.modelType) else self._type
+        th, pi = self._theta, self._pi
+        if mt == "gaussian" or th.ndim != 2 or th.shape[0] != pi.shape[0] or not th.size:
+            return None              # the gaussian type needs the x^2 operand as well
+        if mt == "multinomial":
+            return (th, pi, mt), (lambda: (th, pi)), False
+        if mt == "bernoulli":
+            def make():
+                neg = np.log1p(-np.exp(th))
+                return th - neg, pi + neg.sum(1)
+            return (th, pi, mt), make, False
+        return (th, pi, mt), (lambda: (th, None)), True      # complement
+
+    def __getstate__(self):
+        st = dict(self.__dict__)
+        st.pop("_lp_cache", None)
+        return st
+
     def _raw_sparse(self, X):
         mt = self.getOrDefault(self.modelType) if self.isDefined(self.modelType) else self._type
         th, pi = self._theta, self._pi

@@ -224,6 +224,16 @@ class LogisticRegressionModel(U.ProbabilisticClassifierMixin, Model, _LogisticRe
         b = torch.from_numpy(self._b).to(X.device, W.dtype)
         return (X.to(W.dtype) @ W + b).to(torch.float64)
 
+    def _linear_spec(self):
+        if not self._multinomial or self.numClasses < 2 or self._B.shape[0] != self.numClasses:
+            return None              # binary models keep the margin kernel
+        return (self._B, self._b), (lambda: (self._B, self._b)), False
+
+    def __getstate__(self):
+        st = dict(self.__dict__)
+        st.pop("_lp_cache", None)
+        return st
+
     def _raw2prob(self, raw):
         if not self._multinomial:
             p = torch.sigmoid(raw[:, 1])

@@ -151,14 +151,56 @@ class ProbabilisticClassifierMixin:
             return (prob[:, 1] > self.getOrDefault(self.threshold)).to(torch.float64)
         return prob.argmax(1).to(torch.float64)
 
+    def _linear_spec(self):
+        """Optional hook of a model that scores as softmax(X W^T + b): ``(arrays, make,
+        log_softmax_raw)`` -- the model's own parameter arrays (the cache key, by identity),
+        a callable returning fp64 ``(W [K, d], b [K] or None)`` and whether rawPrediction is
+        the log-softmax of the margins -- or None, which keeps the torch path below."""
+        return None
+
+    def _fused_scores(self, df, feat, want_raw, want_prob, want_pred):
+        """(raw, prob, pred) of the named columns from one launch of the linear scoring
+        kernel over the stored rows, or None: ``_transform`` then runs its torch path."""
+        from ..ops import linear_predict as LP
+        spec = self._linear_spec() if LP.fused_enabled() else None
+        if spec is None:
+            return None
+        arrays, make, lsm = spec
+        K, d = self.numClasses, self.numFeatures
+        if not 1 <= K <= LP.MAX_K or not (want_raw or want_prob or want_pred):
+            return None
+        rows = LP.column_rows(df.column_data(feat), d)
+        if rows is None:
+            return None
+        packed = LP.model_pack(self, arrays, make)
+        # thresholds (or a binary model's threshold) are applied to the probabilities in torch
+        argmax = not ((self.hasParam("thresholds") and self.isSet(self.thresholds))
+                      or (K == 2 and self.hasParam("threshold") and self.isDefined(self.threshold)))
+        raw, prob, pred = LP.linear_predict(rows, d, packed, raw=want_raw,
+                                            prob=want_prob or (want_pred and not argmax),
+                                            pred=want_pred and argmax, log_softmax_raw=lsm)
+        if want_pred and not argmax:
+            pred = self._prob2pred(prob)
+        return raw, prob, pred
+
     def _transform(self, df):
         feat = self.getOrDefault(self.featuresCol)
-        X = self._features_for_predict(df, feat)
-        raw = self._raw(X)
-        out = df
         rc = self.getOrDefault(self.rawPredictionCol) if self.hasParam("rawPredictionCol") else ""
         pc = self.getOrDefault(self.probabilityCol) if self.hasParam("probabilityCol") else ""
         yc = self.getOrDefault(self.predictionCol)
+        fused = self._fused_scores(df, feat, bool(rc), bool(pc), bool(yc))
+        if fused is not None:
+            out = df
+            if rc:
+                out = out.withColumnData(rc, vec_out(fused[0]))
+            if pc:
+                out = out.withColumnData(pc, vec_out(fused[1]))
+            if yc:
+                out = out.withColumnData(yc, num_out(fused[2]))
+            return out
+        X = self._features_for_predict(df, feat)
+        raw = self._raw(X)
+        out = df
         prob = None
         if rc:
             out = out.withColumnData(rc, vec_out(raw))

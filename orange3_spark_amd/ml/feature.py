@@ -1532,9 +1532,21 @@ class PCAModel(Model, _InOut, MLWritable, MLReadable):
         return DenseVector(self._ev)
 
     def _transform(self, df):
-        X = _vec(df, self.getOrDefault(self.inputCol))
+        from ..ops import linear_predict as LP
+        name, d = self.getOrDefault(self.inputCol), int(self._pc.shape[0])
+        rows = LP.column_rows(df.column_data(name), d) if LP.fused_enabled() and self._pc.size else None
+        if rows is not None:          # one pass over the stored rows, no fp64 copy of the table
+            packed = LP.model_pack(self, (self._pc,), lambda: (self._pc.T, None))
+            return df.withColumnData(self.getOrDefault(self.outputCol),
+                                     C.VectorColumn(LP.linear_predict(rows, d, packed)[0]))
+        X = _vec(df, name)
         return df.withColumnData(self.getOrDefault(self.outputCol),
                                  C.VectorColumn(X @ torch.from_numpy(self._pc).to(X.device)))
+
+    def __getstate__(self):
+        st = dict(self.__dict__)
+        st.pop("_lp_cache", None)
+        return st
 
     def _save_data(self, path):
         from .util import mat_col
