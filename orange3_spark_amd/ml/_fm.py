@@ -2,11 +2,15 @@
 
     y(x) = w0 + sum_i w_i x_i + 1/2 sum_f [ (sum_i v_if x_i)^2 - sum_i v_if^2 x_i^2 ]
 
-The pairwise term is two GEMMs per chunk, ``X V`` and ``X^2 V^2`` ([n, D] x [D, F]),
-so a forward/backward pass is GEMM-shaped work for hipBLASLt; the flat gradient
-[V | w | w0] (Spark's parameter layout) is all-reduced once per step
-(models/dist_opt.py).  Solvers: ``adamW`` (Spark's default) and ``gd``, with
-``miniBatchFraction`` sampling.
+On a GPU session whose features column is a plain resident vector column (bf16 or fp32, at
+most 256 columns, ``factorSize`` <= 30) every objective / gradient evaluation of ``fit`` is one
+launch of the fused FM pass over the stored rows and ``transform`` takes its margins from the
+forward half of that kernel (``ops/fm.py``, ``csrc/fm.hip``): no fp32 copy of the table and no
+per-chunk temporaries.  ``O3S_FM_KERNEL=0``, CPU sessions, sparse, lineage and spilled
+columns and wider models run the torch program instead: autograd over row chunks of
+``fm_forward`` (two GEMMs per chunk, ``X V`` and ``X^2 V^2``).  Either way the flat gradient
+[V | w | w0] (Spark's parameter layout) is all-reduced once per step (models/dist_opt.py).
+Solvers: ``adamW`` (Spark's default) and ``gd``, with ``miniBatchFraction`` sampling.
 """
 from __future__ import annotations
 
@@ -14,6 +18,9 @@ import numpy as np
 import torch
 
 from ..models import dist_opt
+from ..ops import fm as FM
+from ..ops import linear_predict as LP
+from ..ops.glm import LOSS_LOGISTIC, LOSS_SQUARED
 from . import common as U
 from .base import Estimator, Model
 from .linalg import DenseMatrix, DenseVector
@@ -48,10 +55,72 @@ def fm_forward(theta: torch.Tensor, X: torch.Tensor, D: int, F: int) -> torch.Te
     return w0 + X @ w + 0.5 * (XV * XV - X2V2).sum(1)
 
 
-def _fit_fm(est, df, classification: bool):
+class _FusedFMObjective(dist_opt.Objective):
+    """The FM objective with the loss and gradient of a row range from one fused pass
+    (``ops.fm.fm_pass``) over the stored rows, in place of autograd over ``fm_forward``.
+
+    ``local`` returns what ``Objective.local`` returns for ``local_loss`` of ``_fit_fm``: the
+    loss sum and the flat fp64 gradient in Spark's layout with ``lin_mask`` applied -- the
+    masked parameters enter the pass as zeros and get zero gradient entries.  The full batch
+    is one launch, a mini-batch one launch per selected chunk.  ``pass_fn`` replaces the
+    kernel wrapper (tests run the objective on the CPU with ``ops.fm.fm_pass_torch``)."""
+
+    def __init__(self, comm, device, X, y, sw, D: int, F: int, loss: int, lin_mask, W: float, l2: float,
+                 l2_mask, chunk: int, pass_fn=None):
+        super().__init__(comm, device, X.shape[0], None, W, l2=l2, l2_mask=l2_mask, chunk=chunk, sw=sw)
+        self.X, self.y, self.D, self.F, self.loss = X, y, D, F, loss
+        self.lin_mask = lin_mask
+        self.grad_mask = lin_mask.to(torch.float64)
+        self.pass_fn = pass_fn
+        self.n = int(X.shape[0])
+
+    def local(self, theta, parts=None):
+        D, F = self.D, self.F
+        fn = self.pass_fn or FM.fm_pass
+        th = theta.detach() * self.lin_mask
+        V, w, w0 = th[: D * F].reshape(D, F), th[D * F: D * F + D], th[-1]
+        total = torch.zeros((), dtype=torch.float64, device=self.device)
+        grad = torch.zeros(D * F + D + 1, dtype=torch.float64, device=self.device)
+        if parts is None or parts is self.parts:
+            parts = [(0, self.n)]                      # the full batch: one launch
+        for a, b in parts:
+            if b <= a:
+                continue
+            gV, gw, gw0, l = fn(self.X[a:b], self.y[a:b], None if self.sw is None else self.sw[a:b], V, w, w0,
+                                self.loss)
+            grad += torch.cat([gV.reshape(-1), gw, gw0.reshape(1)]).to(torch.float64)
+            total += l.to(torch.float64)
+        return total, grad * self.grad_mask
+
+
+def _kernel_rows(df, name: str, F: int):
+    """The stored rows ``[n, d]`` of the features column if the fused FM passes take them -- a
+    plain resident vector column (not lineage, spilled or sparse) that ``fm_kernel_ok`` accepts,
+    with the kernels enabled -- else None."""
+    if not FM.fm_enabled():
+        return None
+    col = df.column_data(name)
+    d = getattr(col, "size", 0)
+    if not 1 <= d <= FM.MAX_D:
+        return None
+    rows = LP.column_rows(col, d)
+    if rows is None:
+        return None
+    X = rows if d == rows.shape[1] else rows[:, :d]
+    return X if FM.fm_kernel_ok(X, F) else None
+
+
+def _fit_fm(est, df, classification: bool, pass_fn=None):
+    """Fit by mini-batch GD / AdamW.  The objective is the fused one when the features column
+    passes :func:`_kernel_rows` (or when ``pass_fn`` is given, which forces the fused objective
+    with that pass function on the dense features), else autograd over row chunks."""
     g = est.getOrDefault
     comm = df.comm
-    X = U.dense_features(df, g(est.featuresCol))
+    F = int(g(est.factorSize))
+    X = None if pass_fn is not None else _kernel_rows(df, g(est.featuresCol), F)
+    fused = X is not None or pass_fn is not None
+    if X is None:
+        X = U.dense_features(df, g(est.featuresCol))
     y = U.numeric_column(df, g(est.labelCol))
     sw = U.weights_or_none(df, est)
     if classification and U.num_classes(comm, y) > 2:
@@ -59,8 +128,10 @@ def _fit_fm(est, df, classification: bool):
     dev = X.device
     dt = dist_opt.compute_dtype(dev)
     n, D = X.shape
-    D = int(comm.max_scalar(float(D)))
-    F = int(g(est.factorSize))
+    Dg = int(comm.max_scalar(float(D)))
+    if Dg != D and fused and pass_fn is None:       # ranks disagree on the width: the torch program pads
+        fused, X = False, U.dense_features(df, g(est.featuresCol))
+    D = Dg
     yt = y.to(dev, dt)
     swt = None if sw is None else sw.to(dev, dt)
     W = float(comm.sum_scalar(float(n if sw is None else sw.sum())))
@@ -86,7 +157,12 @@ def _fit_fm(est, df, classification: bool):
     frac = float(g(est.miniBatchFraction))
     if frac < 1.0:
         chunk = max(1024, min(chunk, int(max(n, 1) * frac) // 4 or 1024))
-    obj = dist_opt.Objective(comm, dev, n, local_loss, W, l2=g(est.regParam), l2_mask=l2_mask, chunk=chunk, sw=swt)
+    if fused:
+        obj = _FusedFMObjective(comm, dev, X, yt, swt, D, F, LOSS_LOGISTIC if classification else LOSS_SQUARED,
+                                lin_mask, W, g(est.regParam), l2_mask, chunk, pass_fn=pass_fn)
+    else:
+        obj = dist_opt.Objective(comm, dev, n, local_loss, W, l2=g(est.regParam), l2_mask=l2_mask, chunk=chunk,
+                                 sw=swt)
     rng = np.random.default_rng(int(g(est.seed)) & 0xFFFFFFFF)
     x0 = np.zeros(D * F + D + 1)
     x0[: D * F] = rng.normal(0.0, g(est.initStd), D * F)
@@ -95,6 +171,13 @@ def _fit_fm(est, df, classification: bool):
                                     seed=int(g(est.seed)) & 0xFFFFFFFF, adam=solver == "adamw")
     x = res.x * lin_mask.double().cpu().numpy()
     return x[: D * F].reshape(D, F), x[D * F: D * F + D], float(x[-1]), res
+
+
+class _KernelRows:
+    """The stored rows of a features column on their way to ``_margin`` (``fm_margin``)."""
+
+    def __init__(self, X: torch.Tensor):
+        self.X = X
 
 
 class _FMModelBase(Model, _FMParams, MLWritable, MLReadable):
@@ -127,7 +210,18 @@ class _FMModelBase(Model, _FMParams, MLWritable, MLReadable):
     def numFeatures(self) -> int:
         return int(self._w.shape[0])
 
+    def _fm_features(self, df, name):
+        """Operand of ``_margin`` for a transform: the stored rows when the margin kernel takes
+        them (:func:`_kernel_rows`), else the dense features."""
+        D, F = self._V.shape
+        X = _kernel_rows(df, name, F)
+        if X is not None and X.shape[1] == D:
+            return _KernelRows(X)
+        return U.dense_features(df, name)
+
     def _margin(self, X):
+        if isinstance(X, _KernelRows):
+            return FM.fm_margin(X.X, torch.from_numpy(self._V), torch.from_numpy(self._w), self._b).to(torch.float64)
         dt = dist_opt.compute_dtype(X.device)
         D, F = self._V.shape
         theta = torch.from_numpy(np.concatenate([self._V.reshape(-1), self._w, [self._b]])).to(X.device, dt)
@@ -195,6 +289,9 @@ class FMClassificationModel(U.ProbabilisticClassifierMixin, _FMModelBase, _FMCla
 
     numClasses = 2
 
+    def _features_for_predict(self, df, name):
+        return self._fm_features(df, name)
+
     def _raw(self, X):
         m = self._margin(X)
         return torch.stack([-m, m], dim=1)
@@ -225,6 +322,9 @@ class FMRegressor(Estimator, _FMParams, MLWritable, MLReadable):
 @register("org.apache.spark.ml.regression.FMRegressionModel")
 class FMRegressionModel(U.PredictionModelMixin, _FMModelBase):
     """Model fitted by FMRegressor."""
+
+    def _features_for_predict(self, df, name):
+        return self._fm_features(df, name)
 
     def _predict_tensor(self, X):
         return self._margin(X)

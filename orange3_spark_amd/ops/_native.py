@@ -124,6 +124,12 @@ _SIGS: dict[str, list] = {
     "o3s_linear_predict_layout": [c_i32, c_i32, C.POINTER(c_i32), C.POINTER(c_i32)],
     "o3s_linear_predict": [c_vp, c_i32, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64,
                            c_i32, c_vp],
+    "o3s_fm_pass": [c_vp, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp,
+                    c_vp],
+    "o3s_fm_pass_f32": [c_vp, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_i32,
+                        c_vp, c_vp],
+    "o3s_fm_margin": [c_vp, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp],
+    "o3s_fm_margin_f32": [c_vp, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp],
 }
 
 
@@ -196,7 +202,7 @@ def host():
 
 PRELOAD_TAGS = ("glm_grad", "glm_mixed", "glm_stats", "glm_softmax", "trees", "kmeans", "als", "als_dense",
                 "als_exact", "assemble", "binsum", "eval", "sampling", "sparse", "text", "probe", "gram", "gmm",
-                "tree_predict", "linear_predict")
+                "tree_predict", "linear_predict", "fm")
 
 
 def preload(tags=PRELOAD_TAGS) -> dict:
