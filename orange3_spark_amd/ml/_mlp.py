@@ -4,9 +4,16 @@ Reached through the Classification widget's reflection.  Network:
 layers with sigmoid activations and a softmax output, cross-entropy loss averaged over
 the (weighted) rows, trained with L-BFGS (default) or gradient descent.
 
-MI355X mapping: every optimiser evaluation runs forward + backward over the rank's rows
-as chunked fp32 GEMMs (hipBLASLt) and all-reduces ONE flat gradient vector
-(models/dist_opt.py) -- data parallelism over row shards, like Spark's treeAggregate.
+MI355X mapping: on a GPU session whose features column is a plain resident vector column
+(bf16 or fp32) a network with one hidden layer (``layers = [d, H, K]``, d <= 256, H <= 128,
+K <= 32 and few enough 32 x 32 blocks of W1, ``ops.mlp.gate_reason``) takes every optimiser
+evaluation from one launch of the fused MLP pass over the stored rows, and ``transform`` takes
+its logits from the forward half of that kernel (``ops/mlp.py``, ``csrc/mlp.hip``): no fp32
+copy of the table and no per-chunk temporaries.  ``O3S_MLP_KERNEL=0``, deeper or wider
+networks, CPU sessions and sparse, lineage and spilled columns run the torch program instead:
+forward + backward over the rank's rows as chunked fp32 GEMMs (hipBLASLt) under autograd.
+Either way ONE flat gradient vector is all-reduced per evaluation (models/dist_opt.py) -- data
+parallelism over row shards, like Spark's treeAggregate.
 The flat weight layout is Spark's (per layer: the [in, out] weight block stored
 column-major as an out x in matrix, then the bias), so saved ``weights`` interoperate.
 """
@@ -16,6 +23,8 @@ import numpy as np
 import torch
 
 from ..models import dist_opt
+from ..ops import linear_predict as LP
+from ..ops import mlp as MLP
 from . import common as U
 from .base import Estimator, Model
 from .linalg import DenseVector
@@ -69,6 +78,67 @@ def init_weights(layers, seed: int) -> np.ndarray:
     return x
 
 
+class _FusedMLPObjective(dist_opt.Objective):
+    """The objective of a ``[d, H, K]`` network with the loss and gradient of a row range from
+    one fused pass (``ops.mlp.mlp_pass``) over the stored rows, in place of autograd over
+    ``forward``.
+
+    ``local`` returns what ``Objective.local`` returns for ``local_loss`` of ``_fit``: the loss
+    sum and the flat fp64 gradient in Spark's layout.  The full batch is one launch, a subset of
+    ``parts`` one launch per chunk.  ``pass_fn`` replaces the kernel wrapper (tests run the
+    objective on the CPU with ``ops.mlp.mlp_pass_torch``)."""
+
+    def __init__(self, comm, device, X, y, layers, W: float, chunk: int = 1 << 18, pass_fn=None):
+        super().__init__(comm, device, X.shape[0], None, W, chunk=chunk)
+        if len(layers) != 3:
+            raise ValueError("the fused MLP objective takes one hidden layer")
+        self.X, self.y, self.layers = X, y, [int(v) for v in layers]
+        self.pass_fn = pass_fn
+        self.n = int(X.shape[0])
+
+    def local(self, theta, parts=None):
+        fn = self.pass_fn or MLP.mlp_pass
+        (sl1, sl2), total_len = layer_slices(self.layers)
+        th = theta.detach()
+        W1, b1 = th[sl1[0]:sl1[1]].reshape(sl1[2], sl1[3]), th[sl1[1]:sl1[1] + sl1[3]]
+        W2, b2 = th[sl2[0]:sl2[1]].reshape(sl2[2], sl2[3]), th[sl2[1]:sl2[1] + sl2[3]]
+        total = torch.zeros((), dtype=torch.float64, device=self.device)
+        grad = torch.zeros(total_len, dtype=torch.float64, device=self.device)
+        if parts is None or parts is self.parts:
+            parts = [(0, self.n)]                      # the full batch: one launch
+        for a, b in parts:
+            if b <= a:
+                continue
+            gW1, gb1, gW2, gb2, l = fn(self.X[a:b], self.y[a:b], W1, b1, W2, b2)
+            grad += torch.cat([gW1.reshape(-1), gb1, gW2.reshape(-1), gb2]).to(torch.float64)
+            total += l.to(torch.float64)
+        return total, grad
+
+
+def _kernel_rows(df, name: str, H: int, K: int):
+    """The stored rows ``[n, d]`` of the features column if the fused MLP passes take them -- a
+    plain resident vector column (not lineage, spilled or sparse) that ``mlp_kernel_ok``
+    accepts, with the kernels enabled -- else None."""
+    if not MLP.mlp_enabled():
+        return None
+    col = df.column_data(name)
+    d = getattr(col, "size", 0)
+    if not 1 <= d <= MLP.MAX_D:
+        return None
+    rows = LP.column_rows(col, d)
+    if rows is None:
+        return None
+    X = rows if d == rows.shape[1] else rows[:, :d]
+    return X if MLP.mlp_kernel_ok(X, H, K) else None
+
+
+class _KernelRows:
+    """The stored rows of a features column on their way to ``_raw`` (``mlp_logits``)."""
+
+    def __init__(self, X: torch.Tensor):
+        self.X = X
+
+
 @register("org.apache.spark.ml.classification.MultilayerPerceptronClassifier")
 class MultilayerPerceptronClassifier(Estimator, _MLPParams, MLWritable, MLReadable):
     """Classifier trainer based on the Multilayer Perceptron. Each layer has sigmoid
@@ -92,7 +162,12 @@ class MultilayerPerceptronClassifier(Estimator, _MLPParams, MLWritable, MLReadab
     def _fit(self, df):
         g = self.getOrDefault
         comm = df.comm
-        X = U.dense_features(df, g(self.featuresCol))
+        sizes = [int(v) for v in g(self.layers)] if self.isDefined(self.layers) and g(self.layers) else []
+        X = _kernel_rows(df, g(self.featuresCol), sizes[1], sizes[2]) if len(sizes) == 3 else None
+        # every fused rank has the input layer's width, so the ranks agree on d
+        fused = X is not None and X.shape[1] == sizes[0]
+        if not fused:
+            X = U.dense_features(df, g(self.featuresCol))
         y = U.numeric_column(df, g(self.labelCol))
         if not self.isDefined(self.layers) or not g(self.layers):
             raise ValueError("MultilayerPerceptronClassifier requires the layers param")
@@ -112,7 +187,10 @@ class MultilayerPerceptronClassifier(Estimator, _MLPParams, MLWritable, MLReadab
             logits = forward(theta, X[a:b].to(dt), layers)
             return torch.nn.functional.cross_entropy(logits, yl[a:b], reduction="sum")
 
-        obj = dist_opt.Objective(comm, dev, n, local_loss, W, chunk=1 << 18)
+        if fused:
+            obj = _FusedMLPObjective(comm, dev, X, yl.to(torch.int32), layers, W, chunk=1 << 18)
+        else:
+            obj = dist_opt.Objective(comm, dev, n, local_loss, W, chunk=1 << 18)
         if self.isDefined(self.initialWeights) and g(self.initialWeights) is not None:
             x0 = np.asarray(g(self.initialWeights).toArray(), dtype=np.float64)
         else:
@@ -170,7 +248,35 @@ class MultilayerPerceptronClassificationModel(U.ProbabilisticClassifierMixin, Mo
     def numClasses(self) -> int:
         return self._layers[-1]
 
+    def _features_for_predict(self, df, name):
+        """Operand of ``_raw`` for a transform: the stored rows when the logits kernel takes
+        them (:func:`_kernel_rows`) and the width matches, else the dense features."""
+        if len(self._layers) == 3:
+            X = _kernel_rows(df, name, self._layers[1], self._layers[2])
+            if X is not None and X.shape[1] == self._layers[0]:
+                return _KernelRows(X)
+        return U.dense_features(df, name)
+
+    def _packed(self, device):
+        """The kernel operands of the weights on ``device``, built at the first use and kept
+        for as long as the weights are the same array."""
+        cache = self.__dict__.get("_mlp_cache")
+        if cache is None or cache[0] is not self._w or cache[1] != device:
+            (sl1, sl2), _ = layer_slices(self._layers)
+            th = torch.from_numpy(self._w)
+            W1, b1 = th[sl1[0]:sl1[1]].reshape(sl1[2], sl1[3]), th[sl1[1]:sl1[1] + sl1[3]]
+            W2, b2 = th[sl2[0]:sl2[1]].reshape(sl2[2], sl2[3]), th[sl2[1]:sl2[1] + sl2[3]]
+            cache = self.__dict__["_mlp_cache"] = (self._w, device, MLP.pack(W1, b1, W2, b2, device=device))
+        return cache[2]
+
+    def __getstate__(self):
+        st = dict(self.__dict__)
+        st.pop("_mlp_cache", None)
+        return st
+
     def _raw(self, X):
+        if isinstance(X, _KernelRows):
+            return MLP.mlp_logits(X.X, None, None, None, None, packed=self._packed(X.X.device)).to(torch.float64)
         dt = dist_opt.compute_dtype(X.device)
         theta = torch.from_numpy(self._w).to(X.device, dt)
         return forward(theta, X.to(dt)[:, : self.numFeatures], self._layers).to(torch.float64)

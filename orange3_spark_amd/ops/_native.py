@@ -130,6 +130,12 @@ _SIGS: dict[str, list] = {
                         c_vp, c_vp],
     "o3s_fm_margin": [c_vp, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp],
     "o3s_fm_margin_f32": [c_vp, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp],
+    "o3s_mlp_pass": [c_vp, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp,
+                     c_vp],
+    "o3s_mlp_pass_f32": [c_vp, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp,
+                         c_vp],
+    "o3s_mlp_logits": [c_vp, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp],
+    "o3s_mlp_logits_f32": [c_vp, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp],
 }
 
 
@@ -202,7 +208,7 @@ def host():
 
 PRELOAD_TAGS = ("glm_grad", "glm_mixed", "glm_stats", "glm_softmax", "trees", "kmeans", "als", "als_dense",
                 "als_exact", "assemble", "binsum", "eval", "sampling", "sparse", "text", "probe", "gram", "gmm",
-                "tree_predict", "linear_predict", "fm")
+                "tree_predict", "linear_predict", "fm", "mlp")
 
 
 def preload(tags=PRELOAD_TAGS) -> dict:
