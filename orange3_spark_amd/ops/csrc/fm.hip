@@ -9,16 +9,13 @@
 // Reference: Spark's FMClassifier / FMRegressor gradient (BaseFactorizationMachinesGradient),
 // reached from the classification and regression widgets.
 //
-// An FM pass is the multinomial pass of glm_softmax.hip with another epilogue, and the
-// kernels keep that file's structure: 256 threads = 4 independent waves, 32-row tiles,
-// v_mfma_f32_32x32x16_bf16 with lane (r = lane&31, h = lane>>5), the row's own global loads
-// as the forward B operand, the next tile prefetched into a second register copy, per-wave
-// slab rows summed in fp64 by glm_finish_kernel in a fixed order.  No float atomics, and the
-// same bits for any grid: slab row v sums the tiles v, v + nslab, ..., one wave per slab row, and
-// a grid with fewer waves than slab rows is launched as often as it takes (fm_launch).
+// An FM pass is the multinomial pass of glm_softmax.hip with another epilogue, on the tile of
+// mfma_tile.h: 256 threads = 4 independent waves, per-wave slab rows.  The same bits for any
+// grid: slab row v sums the tiles v, v + nslab, ..., one wave per slab row, and a grid with fewer
+// waves than slab rows is launched as often as it takes (fm_launch).
 //   forward  A = the hi + mid + lo bf16 split of the "classes" [V columns (F) | w], zero
 //            padded to 32 -> acc[v] = q_f (class < F) or the linear term (class F) of row
-//            r, class 8(v>>2) + 4h + (v&3).  sum_i s_i x_i^2 is an in-lane fp32 FMA over
+//            r, class 4h + mt_cv(v).  sum_i s_i x_i^2 is an in-lane fp32 FMA over
 //            the lane's 8 columns per k-step (s as floats in LDS), sum_f q_f^2 an in-lane
 //            sum over the lane's accumulator registers; one __shfl_xor(.., 32) combines
 //            the two halves of a row.
@@ -33,37 +30,29 @@
 // Hence F <= 30.  No scratch in any instantiation at the one wave per SIMD the wide ones run
 // at (the table is in doc/performance.md).
 #include "glm_launch.h"
+#include "mfma_tile.h"
 
 namespace {
 
-typedef float fm_f32x16 __attribute__((ext_vector_type(16)));
-typedef short fm_bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t fm_u32x4 __attribute__((ext_vector_type(4)));
 constexpr int kFmWaves = 4;
 constexpr int kFmThreads = kFmWaves * kWave;
 
 template <int NB, bool MARGIN>
-struct FmLds {
-  static constexpr int D = 32 * NB;
-  static constexpr int WLD = D + 8;     // +16 B per row: conflict-free 16-B fragment reads
-  static constexpr int XLD = D + 8;
-  static constexpr int RLD = 40;        // 80-B rows: the 16-B R fragment reads hit distinct banks
-  static constexpr int W_ELEMS = 3 * 32 * WLD;
+struct FmLds : MtPitch<NB> {
+  using P = MtPitch<NB>;
+  static constexpr int W_ELEMS = 3 * 32 * P::WLD;
   // per wave: the tile for the X^T reads, R hi + lo [2][32][RLD], and r hi + lo [2][RLD]
-  static constexpr int WAVE_ELEMS = MARGIN ? 0 : 32 * XLD + 2 * 32 * RLD + 2 * RLD;
+  static constexpr int WAVE_ELEMS = MARGIN ? 0 : 32 * P::XLD + 2 * 32 * P::RLD + 2 * P::RLD;
   static constexpr int ELEMS = W_ELEMS + kFmWaves * WAVE_ELEMS;
 };
 
-// register v of a lane's accumulator tile is class 4 h + fm_cv(v)
-__device__ __forceinline__ constexpr int fm_cv(int v) { return 8 * (v >> 2) + (v & 3); }
-
 // The margin of row r from its accumulators (q_f, linear term), sx = this lane's share of
 // sum_i s_i x_i^2, and w0 = w0h + w0l.  Both halves of the row return the same bits.
-__device__ __forceinline__ float fm_margin_of(const fm_f32x16& acc, float sx, int F, int h, float w0h, float w0l) {
+__device__ __forceinline__ float fm_margin_of(const mt_f32x16& acc, float sx, int F, int h, float w0h, float w0l) {
   float qq = 0.f, lin = 0.f;
 #pragma unroll
   for (int v = 0; v < 16; ++v) {
-    const int c = 4 * h + fm_cv(v);
+    const int c = 4 * h + mt_cv(v);
     qq = c < F ? fmaf(acc[v], acc[v], qq) : qq;
     lin = c == F ? acc[v] : lin;
   }
@@ -73,66 +62,178 @@ __device__ __forceinline__ float fm_margin_of(const fm_f32x16& acc, float sx, in
 
 // The residual matrix of the tile -> LDS: class f < F is rr q_f, class F is rr, the rest 0,
 // as hi + lo bf16 (Rw = Rs + 4 h RLD + r); rr itself as hi + lo for the x^2 product (Rq).
-__device__ __forceinline__ void fm_store_r(const fm_f32x16& acc, float rr, int F, int h, int r, uint16_t* Rw,
+__device__ __forceinline__ void fm_store_r(const mt_f32x16& acc, float rr, int F, int h, int r, uint16_t* Rw,
                                            uint16_t* Rq, int RLD) {
 #pragma unroll
   for (int v = 0; v < 16; v += 2) {
     float rv[2];
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
-      const int c = 4 * h + fm_cv(v + u);
+      const int c = 4 * h + mt_cv(v + u);
       rv[u] = c < F ? rr * acc[v + u] : (c == F ? rr : 0.f);
     }
-    const uint32_t ph = pk_bf16(rv[0], rv[1]);
-    const uint32_t pl = pk_bf16(rv[0] - __uint_as_float(ph << 16), rv[1] - __uint_as_float(ph & 0xffff0000u));
-    Rw[fm_cv(v) * RLD] = (uint16_t)ph;
-    Rw[fm_cv(v + 1) * RLD] = (uint16_t)(ph >> 16);
-    Rw[(32 + fm_cv(v)) * RLD] = (uint16_t)pl;
-    Rw[(32 + fm_cv(v + 1)) * RLD] = (uint16_t)(pl >> 16);
+    mt_store_r_pair(Rw, v, rv[0], rv[1], RLD);
   }
   if (h == 0) {
-    const uint32_t ph = pk_bf16(rr, 0.f);
-    const uint32_t pl = pk_bf16(rr - __uint_as_float(ph << 16), 0.f);
+    uint32_t ph, pl;
+    split_bf16x2(rr, 0.f, ph, pl);
     Rq[r] = (uint16_t)ph;
     Rq[RLD + r] = (uint16_t)pl;
   }
 }
 
 // 8 squares -> two bf16 terms each (hi + lo of the fp32 product).
-__device__ __forceinline__ void fm_square8(const float (&x)[8], fm_bf16x8& hi, fm_bf16x8& lo) {
-  fm_u32x4 ph, pl;
+__device__ __forceinline__ void fm_square8(const float (&x)[8], mt_bf16x8& hi, mt_bf16x8& lo) {
+  mt_u32x4 ph, pl;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    const float a = x[2 * j] * x[2 * j], b = x[2 * j + 1] * x[2 * j + 1];
-    ph[j] = pk_bf16(a, b);
-    pl[j] = pk_bf16(a - __uint_as_float(ph[j] << 16), b - __uint_as_float(ph[j] & 0xffff0000u));
+    uint32_t h, l;
+    split_bf16x2(x[2 * j] * x[2 * j], x[2 * j + 1] * x[2 * j + 1], h, l);
+    ph[j] = h;
+    pl[j] = l;
   }
-  hi = __builtin_bit_cast(fm_bf16x8, ph);
-  lo = __builtin_bit_cast(fm_bf16x8, pl);
+  hi = __builtin_bit_cast(mt_bf16x8, ph);
+  lo = __builtin_bit_cast(mt_bf16x8, pl);
 }
 
-// This wave's slab row: [G class-major 32 x D | sum r | 31 zeros | loss].
-template <int NB>
-__device__ __forceinline__ void fm_write_slab(const fm_f32x16 (&G)[NB], float racc, float lossacc, int r, int h,
-                                              int lane, float* out) {
-  constexpr int D = 32 * NB;
+// The R and r fragments of 16-row step rs: ar = R hi, lo; aq = r hi, lo in lane F + 1, else 0.
+__device__ __forceinline__ void fm_read_r(const uint16_t* Rs, const uint16_t* Rq, int rs, int F, int r, int h, int RLD,
+                                          mt_bf16x8 (&ar)[2], mt_bf16x8 (&aq)[2]) {
 #pragma unroll
-  for (int b = 0; b < NB; ++b)
-#pragma unroll
-    for (int v = 0; v < 16; ++v) out[(4 * h + fm_cv(v)) * D + b * 32 + r] = G[b][v];
-  const float rt = wave_sum(racc), lt = wave_sum(lossacc);
-  if (lane < 32) out[32 * D + lane] = lane == 0 ? rt : 0.f;
-  if (lane == 0) out[32 * D + 32] = lt;
+  for (int s = 0; s < 2; ++s) {
+    ar[s] = *reinterpret_cast<const mt_bf16x8*>(Rs + (s * 32 + r) * RLD + rs * 16 + 8 * h);
+    const mt_bf16x8 t = *reinterpret_cast<const mt_bf16x8*>(Rq + s * RLD + rs * 16 + 8 * h);
+    const mt_bf16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+    aq[s] = r == F + 1 ? t : z;
+  }
 }
 
-template <int NB, int LOSS, bool MARGIN = false>
-__global__ __launch_bounds__(kFmThreads, 1) void fm_pass_kernel(
-    const uint16_t* __restrict__ X, int64_t n, int64_t ldx, const float* __restrict__ y,
-    const float* __restrict__ sw, const uint16_t* __restrict__ Wsp, const float* __restrict__ sv,
-    const float* __restrict__ w0p, int F, float* __restrict__ partial, int pstride, int nslab,
-    int slab0, float* __restrict__ margin) {
+// The two tile steps.  forward: acc += [V^T | w] x and sx += sum_i s_i x_i^2 over the lane's
+// columns of row r; backward: G += R^T X and row F + 1 += r x^2 over the tile's rows.
+// bf16 rows: the tile goes to LDS as it is, once, and is read back transposed.
+struct FmRowsBf16 : MtBf16 {
+  template <int KS> struct terms {};
+  template <int KS, bool MARGIN>
+  __device__ static __forceinline__ void forward(const chunk (&xb)[KS], terms<KS>&, const uint16_t* Ws, const float* ss,
+                                                 uint16_t* Xs, int r, int h, mt_f32x16& acc, float& sx) {
+    constexpr int WLD = MtPitch<KS / 2>::WLD, XLD = MtPitch<KS / 2>::XLD;
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+      const uint16_t* wp = Ws + r * WLD + ks * 16 + 8 * h;
+      acc = mt_mfma3(acc, *reinterpret_cast<const mt_bf16x8*>(wp), *reinterpret_cast<const mt_bf16x8*>(wp + 32 * WLD),
+                     *reinterpret_cast<const mt_bf16x8*>(wp + 64 * WLD), xb[ks]);
+      if (!MARGIN) *reinterpret_cast<mt_bf16x8*>(Xs + r * XLD + ks * 16 + 8 * h) = xb[ks];   // for the X^T reads
+      const float4_ s0 = *reinterpret_cast<const float4_*>(ss + ks * 16 + 8 * h);
+      const float4_ s1 = *reinterpret_cast<const float4_*>(ss + ks * 16 + 8 * h + 4);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float xv = bf16_to_f32((uint16_t)xb[ks][j]);
+        sx = fmaf((j < 4 ? s0[j] : s1[j - 4]) * xv, xv, sx);
+      }
+    }
+  }
+  template <int NB>
+  __device__ static __forceinline__ void backward(const terms<2 * NB>&, uint16_t* Xs, const uint16_t* Rs,
+                                                  const uint16_t* Rq, int F, int r, int h, mt_f32x16 (&G)[NB]) {
+    constexpr int XLD = MtPitch<NB>::XLD, RLD = MtPitch<NB>::RLD;
+    mt_bf16x8 ar[2][2], aq[2][2];
+#pragma unroll
+    for (int rs = 0; rs < 2; ++rs) fm_read_r(Rs, Rq, rs, F, r, h, RLD, ar[rs], aq[rs]);
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+#pragma unroll
+      for (int rs = 0; rs < 2; ++rs) {
+        const mt_bf16x8 bx = mt_read_xt(Xs, rs * 16 + 8 * h, b * 32 + r, XLD);
+        mt_bf16x8 qh, ql;
+        float xv[8];
+        unpack8(bx, xv);
+        fm_square8(xv, qh, ql);
+#pragma unroll
+        for (int s = 0; s < 2; ++s) G[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[rs][s], bx, G[b], 0, 0, 0);
+        G[b] = mt_mfma4(G[b], aq[rs][0], aq[rs][1], qh, ql);
+      }
+    }
+    mt_wave_sync();    // tile's LDS reads done before it is overwritten
+  }
+};
+// fp32 rows.  As in glm_softmax_f32_kernel a row is split into bf16 terms as it is consumed:
+// hi + mid + lo forward with the six products of order <= 2 (margins and loss at fp32 level),
+// hi + mid backward, staged through LDS 16 rows (one MFMA k-step) at a time (Xs is
+// [hi, mid][16 rows][XLD]).  sum_i s_i x_i^2 takes the fp32 values before the split.  x^2 for t
+// is the fp32 square of hi + mid read back transposed, split into two bf16 terms.  The class of
+// an accumulator register is recomputed from the lane id and the R fragments are read per 16-row
+// step, to keep the NB = 8 instantiation out of scratch.
+struct FmRowsF32 : MtF32 {
+  template <int KS> struct terms { mt_bf16x8 xh[KS], xm[KS]; };   // stay in the registers the fp32 values came in
+  template <int KS, bool MARGIN>
+  __device__ static __forceinline__ void forward(const chunk (&xf)[KS], terms<KS>& t, const uint16_t* Ws,
+                                                 const float* ss, uint16_t*, int r, int h, mt_f32x16& acc, float& sx) {
+    constexpr int WLD = MtPitch<KS / 2>::WLD;
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+      const float4_ s0 = *reinterpret_cast<const float4_*>(ss + ks * 16 + 8 * h);
+      const float4_ s1 = *reinterpret_cast<const float4_*>(ss + ks * 16 + 8 * h + 4);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        sx = fmaf(s0[j] * xf[ks].a[j], xf[ks].a[j], sx);
+        sx = fmaf(s1[j] * xf[ks].b[j], xf[ks].b[j], sx);
+      }
+      mt_bf16x8 xl;
+      mt_split8(xf[ks].a, xf[ks].b, t.xh[ks], t.xm[ks], xl);
+      const uint16_t* wp = Ws + r * WLD + ks * 16 + 8 * h;
+      acc = mt_mfma6(acc, *reinterpret_cast<const mt_bf16x8*>(wp), *reinterpret_cast<const mt_bf16x8*>(wp + 32 * WLD),
+                     *reinterpret_cast<const mt_bf16x8*>(wp + 64 * WLD), t.xh[ks], t.xm[ks], xl);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+  template <int NB>
+  __device__ static __forceinline__ void backward(const terms<2 * NB>& t, uint16_t* Xs, const uint16_t* Rs,
+                                                  const uint16_t* Rq, int F, int r, int h, mt_f32x16 (&G)[NB]) {
+    constexpr int KS = 2 * NB, XLD = MtPitch<NB>::XLD, RLD = MtPitch<NB>::RLD;
+#pragma unroll
+    for (int rs = 0; rs < 2; ++rs) {
+      if ((r >> 4) == rs) {
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+          *reinterpret_cast<mt_bf16x8*>(Xs + (r & 15) * XLD + ks * 16 + 8 * h) = t.xh[ks];
+          *reinterpret_cast<mt_bf16x8*>(Xs + (16 + (r & 15)) * XLD + ks * 16 + 8 * h) = t.xm[ks];
+        }
+      }
+      mt_bf16x8 ar[2], aq[2];
+      fm_read_r(Rs, Rq, rs, F, r, h, RLD, ar, aq);
+      mt_wave_sync();
+#pragma unroll
+      for (int b = 0; b < NB; ++b) {
+        // (mt_read_xt of hi and mid, and their sum, element by element in one loop: read apart, hipcc
+        // forms the sums with scalar adds in place of packed ones)
+        mt_bf16x8 bh, bm, qh, ql;
+        float xv[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          bh[q] = (short)Xs[(8 * h + q) * XLD + b * 32 + r];
+          bm[q] = (short)Xs[(16 + 8 * h + q) * XLD + b * 32 + r];
+          xv[q] = bf16_to_f32((uint16_t)bh[q]) + bf16_to_f32((uint16_t)bm[q]);
+        }
+        fm_square8(xv, qh, ql);
+        G[b] = mt_mfma4(G[b], ar[0], ar[1], bh, bm);
+        G[b] = mt_mfma4(G[b], aq[0], aq[1], qh, ql);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      mt_wave_sync();    // staged reads done before the area is overwritten
+    }
+  }
+};
+
+// What the two passes share: the prologue, the slab walk, the prefetch, everything between the
+// forward and the backward products of a tile, and the slab row.
+template <class SRC, int NB, int LOSS, bool MARGIN>
+__device__ __forceinline__ void fm_body(const typename SRC::elem* __restrict__ X, int64_t n, int64_t ldx,
+                                        const float* __restrict__ y, const float* __restrict__ sw,
+                                        const uint16_t* __restrict__ Wsp, const float* __restrict__ sv,
+                                        const float* __restrict__ w0p, int F, float* __restrict__ partial, int pstride,
+                                        int nslab, int slab0, float* __restrict__ margin) {
   using L = FmLds<NB, MARGIN>;
-  constexpr int D = L::D, KS = 2 * NB, WLD = L::WLD, XLD = L::XLD, RLD = L::RLD;
+  constexpr int D = L::D, KS = 2 * NB, XLD = L::XLD, RLD = L::RLD;
   __shared__ __attribute__((aligned(16))) uint16_t smem[L::ELEMS];
   __shared__ __attribute__((aligned(16))) float ss[D];   // s_i, zero past d
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -142,12 +243,7 @@ __global__ __launch_bounds__(kFmThreads, 1) void fm_pass_kernel(
   uint16_t* Rs = Xs + 32 * XLD;
   uint16_t* Rq = Rs + 2 * 32 * RLD;
 
-  // class splits [3][32][D] -> LDS (padded rows)
-  for (int p = threadIdx.x; p < 3 * 32 * (D / 8); p += kFmThreads) {
-    const int row = p / (D / 8), k8 = p % (D / 8);
-    *reinterpret_cast<fm_bf16x8*>(Ws + row * WLD + k8 * 8) =
-        *reinterpret_cast<const fm_bf16x8*>(Wsp + (int64_t)row * D + k8 * 8);
-  }
+  mt_stage_w<3 * 32, NB, kFmThreads>(Ws, Wsp);
   for (int p = threadIdx.x; p < D; p += kFmThreads) ss[p] = sv[p];
   const float w0h = w0p[0], w0l = w0p[1];
   __syncthreads();
@@ -159,55 +255,26 @@ __global__ __launch_bounds__(kFmThreads, 1) void fm_pass_kernel(
   const int64_t step = nslab;
   const int slab = slab0 + blockIdx.x * kFmWaves + wid;
   if (slab >= nslab) return;   // the waves are independent from here on
-  fm_f32x16 G[NB];
+  mt_f32x16 G[NB];
 #pragma unroll
   for (int b = 0; b < NB; ++b)
 #pragma unroll
     for (int v = 0; v < 16; ++v) G[b][v] = 0.f;
   float racc = 0.f, lossacc = 0.f;
   int64_t tile = slab;
-  fm_bf16x8 xb[KS], xn[KS];
-  auto load = [&](int64_t t, fm_bf16x8 (&dst)[KS]) {
-    int64_t row = t * 32 + r;
-    row = row < n ? row : n - 1;
-    const uint16_t* src = X + row * ldx;
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      const int col = ks * 16 + 8 * h;
-      if (col < ldx) {
-        dst[ks] = *reinterpret_cast<const fm_bf16x8*>(src + col);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) dst[ks][j] = 0;
-      }
-    }
-  };
-  if (tile < ntiles) load(tile, xb);
+  typename SRC::chunk xc[KS], xn[KS];
+  if (tile < ntiles) mt_load_tile<SRC, KS>(X, n, ldx, tile, r, h, xc);
   for (; tile < ntiles; tile += step) {
-    if (tile + step < ntiles) load(tile + step, xn);
+    if (tile + step < ntiles) mt_load_tile<SRC, KS>(X, n, ldx, tile + step, r, h, xn);
     const int64_t row = tile * 32 + r;
     const bool valid = row < n;
     // ---- forward: q_f and the linear term of row r, 16 classes per lane
-    fm_f32x16 acc;
+    mt_f32x16 acc;
 #pragma unroll
     for (int v = 0; v < 16; ++v) acc[v] = 0.f;
     float sx = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-#pragma unroll
-      for (int s = 0; s < 3; ++s) {
-        const fm_bf16x8 a = *reinterpret_cast<const fm_bf16x8*>(Ws + (s * 32 + r) * WLD + ks * 16 + 8 * h);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, xb[ks], acc, 0, 0, 0);
-      }
-      if (!MARGIN) *reinterpret_cast<fm_bf16x8*>(Xs + r * XLD + ks * 16 + 8 * h) = xb[ks];   // for the X^T reads
-      const float4_ s0 = *reinterpret_cast<const float4_*>(ss + ks * 16 + 8 * h);
-      const float4_ s1 = *reinterpret_cast<const float4_*>(ss + ks * 16 + 8 * h + 4);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float xv = bf16_to_f32((uint16_t)xb[ks][j]);
-        sx = fmaf((j < 4 ? s0[j] : s1[j - 4]) * xv, xv, sx);
-      }
-    }
+    typename SRC::template terms<KS> xt;
+    SRC::template forward<KS, MARGIN>(xc, xt, Ws, ss, Xs, r, h, acc, sx);
     const float m = fm_margin_of(acc, sx, F, h, w0h, w0l);
     if (MARGIN) {
       if (h == 0 && valid) margin[row] = m;
@@ -221,74 +288,29 @@ __global__ __launch_bounds__(kFmThreads, 1) void fm_pass_kernel(
         lossacc += ll;
       }
       fm_store_r(acc, rr, F, h, r, Rs + 4 * h * RLD + r, Rq, RLD);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_wave_barrier();
-      // ---- backward: G[class][dim] += sum over the tile's rows of R[row][class] X[row][dim],
-      // and row F + 1 += r x^2
-      fm_bf16x8 ar[2][2], aq[2][2];
-#pragma unroll
-      for (int rs = 0; rs < 2; ++rs)
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-          ar[rs][s] = *reinterpret_cast<const fm_bf16x8*>(Rs + (s * 32 + r) * RLD + rs * 16 + 8 * h);
-          const fm_bf16x8 t = *reinterpret_cast<const fm_bf16x8*>(Rq + s * RLD + rs * 16 + 8 * h);
-          const fm_bf16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
-          aq[rs][s] = r == F + 1 ? t : z;
-        }
-#pragma unroll
-      for (int b = 0; b < NB; ++b) {
-#pragma unroll
-        for (int rs = 0; rs < 2; ++rs) {
-          fm_bf16x8 bx, qh, ql;
-          float xv[8];
-#pragma unroll
-          for (int q = 0; q < 8; ++q) {
-            bx[q] = (short)Xs[(rs * 16 + 8 * h + q) * XLD + b * 32 + r];
-            xv[q] = bf16_to_f32((uint16_t)bx[q]);
-          }
-          fm_square8(xv, qh, ql);
-#pragma unroll
-          for (int s = 0; s < 2; ++s) G[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[rs][s], bx, G[b], 0, 0, 0);
-          G[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(aq[rs][1], ql, G[b], 0, 0, 0);
-          G[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(aq[rs][0], ql, G[b], 0, 0, 0);
-          G[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(aq[rs][1], qh, G[b], 0, 0, 0);
-          G[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(aq[rs][0], qh, G[b], 0, 0, 0);
-        }
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    // tile's LDS reads done before it is overwritten
-      __builtin_amdgcn_wave_barrier();
+      mt_wave_sync();
+      SRC::template backward<NB>(xt, Xs, Rs, Rq, F, r, h, G);
     }
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) xb[ks] = xn[ks];
+    for (int ks = 0; ks < KS; ++ks) xc[ks] = xn[ks];
   }
-  if (!MARGIN) fm_write_slab<NB>(G, racc, lossacc, r, h, lane, partial + (int64_t)slab * pstride);
+  if (!MARGIN) {
+    // ---- this wave's slab row: [G class-major 32 x D | sum r | 31 zeros | loss]
+    float* out = partial + (int64_t)slab * pstride;
+    mt_write_slab_g<NB>(G, out, r, h);
+    const float rt = wave_sum(racc), lt = wave_sum(lossacc);
+    if (lane < 32) out[32 * D + lane] = lane == 0 ? rt : 0.f;
+    if (lane == 0) out[32 * D + 32] = lt;
+  }
 }
 
-// ---------------------------------------------------------------------------------
-// The pass over fp32 rows: the contract, layouts and slab rows of fm_pass_kernel for
-// X = float [n, ldx].  As in glm_softmax_f32_kernel a row is split into bf16 terms as it is
-// consumed: hi + mid + lo forward with the six products of order <= 2 (margins and loss at
-// fp32 level), hi + mid backward, staged through LDS 16 rows (one MFMA k-step) at a time.
-// sum_i s_i x_i^2 takes the fp32 values before the split.  x^2 for t is the fp32 square of
-// hi + mid read back transposed, split into two bf16 terms.  The class of an accumulator
-// register is recomputed from the lane id and the R fragments are read per 16-row step, to
-// keep the NB = 8 instantiation out of scratch.
-// 8 fp32 -> bf16 terms hi + mid + lo (split_bf16x3 of glm_rows.h, pair by pair).
-__device__ __forceinline__ void fm_split8(const float4_ a, const float4_ b, fm_bf16x8& hi, fm_bf16x8& mid,
-                                          fm_bf16x8& lo) {
-  fm_u32x4 ph, pm, pl;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float x0 = j < 2 ? a[2 * j] : b[2 * j - 4], x1 = j < 2 ? a[2 * j + 1] : b[2 * j - 3];
-    uint32_t h, m, l;
-    split_bf16x3(x0, x1, h, m, l);
-    ph[j] = h;
-    pm[j] = m;
-    pl[j] = l;
-  }
-  hi = __builtin_bit_cast(fm_bf16x8, ph);
-  mid = __builtin_bit_cast(fm_bf16x8, pm);
-  lo = __builtin_bit_cast(fm_bf16x8, pl);
+template <int NB, int LOSS, bool MARGIN = false>
+__global__ __launch_bounds__(kFmThreads, 1) void fm_pass_kernel(
+    const uint16_t* __restrict__ X, int64_t n, int64_t ldx, const float* __restrict__ y,
+    const float* __restrict__ sw, const uint16_t* __restrict__ Wsp, const float* __restrict__ sv,
+    const float* __restrict__ w0p, int F, float* __restrict__ partial, int pstride, int nslab,
+    int slab0, float* __restrict__ margin) {
+  fm_body<FmRowsBf16, NB, LOSS, MARGIN>(X, n, ldx, y, sw, Wsp, sv, w0p, F, partial, pstride, nslab, slab0, margin);
 }
 
 template <int NB, int LOSS, bool MARGIN = false>
@@ -297,159 +319,7 @@ __global__ __launch_bounds__(kFmThreads, 1) void fm_pass_f32_kernel(
     const float* __restrict__ sw, const uint16_t* __restrict__ Wsp, const float* __restrict__ sv,
     const float* __restrict__ w0p, int F, float* __restrict__ partial, int pstride, int nslab,
     int slab0, float* __restrict__ margin) {
-  using L = FmLds<NB, MARGIN>;
-  constexpr int D = L::D, KS = 2 * NB, WLD = L::WLD, XLD = L::XLD, RLD = L::RLD;
-  __shared__ __attribute__((aligned(16))) uint16_t smem[L::ELEMS];
-  __shared__ __attribute__((aligned(16))) float ss[D];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int r = lane & 31, h = lane >> 5;
-  uint16_t* Ws = smem;
-  uint16_t* Xs = smem + L::W_ELEMS + wid * L::WAVE_ELEMS;   // [hi, mid][16 rows][XLD]
-  uint16_t* Rs = Xs + 32 * XLD;
-  uint16_t* Rq = Rs + 2 * 32 * RLD;
-
-  for (int p = threadIdx.x; p < 3 * 32 * (D / 8); p += kFmThreads) {
-    const int row = p / (D / 8), k8 = p % (D / 8);
-    *reinterpret_cast<fm_bf16x8*>(Ws + row * WLD + k8 * 8) =
-        *reinterpret_cast<const fm_bf16x8*>(Wsp + (int64_t)row * D + k8 * 8);
-  }
-  for (int p = threadIdx.x; p < D; p += kFmThreads) ss[p] = sv[p];
-  const float w0h = w0p[0], w0l = w0p[1];
-  __syncthreads();
-
-  // Slab row v sums the tiles v, v + nslab, ... (nslab <= the number of tiles), and this wave
-  // holds slab row slab0 + its index in the grid: how many blocks a launch has decides which
-  // wave sums a slab row, not what the row holds.
-  const int64_t ntiles = (n + 31) / 32;
-  const int64_t step = nslab;
-  const int slab = slab0 + blockIdx.x * kFmWaves + wid;
-  if (slab >= nslab) return;   // the waves are independent from here on
-  fm_f32x16 G[NB];
-#pragma unroll
-  for (int b = 0; b < NB; ++b)
-#pragma unroll
-    for (int v = 0; v < 16; ++v) G[b][v] = 0.f;
-  float racc = 0.f, lossacc = 0.f;
-  int64_t tile = slab;
-  float4_ xf[KS][2], xn[KS][2];
-  auto load = [&](int64_t t, float4_ (*dst)[2]) {
-    int64_t row = t * 32 + r;
-    row = row < n ? row : n - 1;
-    const float* src = X + row * ldx;
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      const int col = ks * 16 + 8 * h;
-      if (col < ldx) {
-        dst[ks][0] = *reinterpret_cast<const float4_*>(src + col);
-        dst[ks][1] = *reinterpret_cast<const float4_*>(src + col + 4);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) dst[ks][0][j] = dst[ks][1][j] = 0.f;
-      }
-    }
-  };
-  if (tile < ntiles) load(tile, xf);
-  for (; tile < ntiles; tile += step) {
-    if (tile + step < ntiles) load(tile + step, xn);
-    const int64_t row = tile * 32 + r;
-    const bool valid = row < n;
-    // ---- forward; the hi and mid terms of the row stay in the registers the fp32 values
-    // came in, for the backward staging below
-    fm_f32x16 acc;
-#pragma unroll
-    for (int v = 0; v < 16; ++v) acc[v] = 0.f;
-    float sx = 0.f;
-    fm_bf16x8 xh[KS], xm[KS];
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      const float4_ s0 = *reinterpret_cast<const float4_*>(ss + ks * 16 + 8 * h);
-      const float4_ s1 = *reinterpret_cast<const float4_*>(ss + ks * 16 + 8 * h + 4);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        sx = fmaf(s0[j] * xf[ks][0][j], xf[ks][0][j], sx);
-        sx = fmaf(s1[j] * xf[ks][1][j], xf[ks][1][j], sx);
-      }
-      fm_bf16x8 xl;
-      fm_split8(xf[ks][0], xf[ks][1], xh[ks], xm[ks], xl);
-      const uint16_t* wp = Ws + r * WLD + ks * 16 + 8 * h;
-      const fm_bf16x8 a0 = *reinterpret_cast<const fm_bf16x8*>(wp);
-      const fm_bf16x8 a1 = *reinterpret_cast<const fm_bf16x8*>(wp + 32 * WLD);
-      const fm_bf16x8 a2 = *reinterpret_cast<const fm_bf16x8*>(wp + 64 * WLD);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, xl, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, xh[ks], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, xm[ks], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, xm[ks], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, xh[ks], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, xh[ks], acc, 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    const float m = fm_margin_of(acc, sx, F, h, w0h, w0l);
-    if (MARGIN) {
-      if (h == 0 && valid) margin[row] = m;
-    } else {
-      const float yv = valid ? y[row] : 0.f;
-      const float wr = valid ? (sw ? sw[row] : 1.f) : 0.f;
-      float rr, ll;
-      loss_terms<LOSS>(m, yv, wr, rr, ll);
-      if (h == 0) {
-        racc += rr;
-        lossacc += ll;
-      }
-      fm_store_r(acc, rr, F, h, r, Rs + 4 * h * RLD + r, Rq, RLD);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_wave_barrier();
-      // ---- backward, 16 rows (one MFMA k-step) at a time through this wave's staging area
-#pragma unroll
-      for (int rs = 0; rs < 2; ++rs) {
-        if ((r >> 4) == rs) {
-#pragma unroll
-          for (int ks = 0; ks < KS; ++ks) {
-            *reinterpret_cast<fm_bf16x8*>(Xs + (r & 15) * XLD + ks * 16 + 8 * h) = xh[ks];
-            *reinterpret_cast<fm_bf16x8*>(Xs + (16 + (r & 15)) * XLD + ks * 16 + 8 * h) = xm[ks];
-          }
-        }
-        fm_bf16x8 ar[2], aq[2];
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-          ar[s] = *reinterpret_cast<const fm_bf16x8*>(Rs + (s * 32 + r) * RLD + rs * 16 + 8 * h);
-          const fm_bf16x8 t = *reinterpret_cast<const fm_bf16x8*>(Rq + s * RLD + rs * 16 + 8 * h);
-          const fm_bf16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
-          aq[s] = r == F + 1 ? t : z;
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int b = 0; b < NB; ++b) {
-          fm_bf16x8 bh, bm, qh, ql;
-          float xv[8];
-#pragma unroll
-          for (int q = 0; q < 8; ++q) {
-            bh[q] = (short)Xs[(8 * h + q) * XLD + b * 32 + r];
-            bm[q] = (short)Xs[(16 + 8 * h + q) * XLD + b * 32 + r];
-            xv[q] = bf16_to_f32((uint16_t)bh[q]) + bf16_to_f32((uint16_t)bm[q]);
-          }
-          fm_square8(xv, qh, ql);
-          G[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[1], bm, G[b], 0, 0, 0);
-          G[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[0], bm, G[b], 0, 0, 0);
-          G[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[1], bh, G[b], 0, 0, 0);
-          G[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[0], bh, G[b], 0, 0, 0);
-          G[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(aq[1], ql, G[b], 0, 0, 0);
-          G[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(aq[0], ql, G[b], 0, 0, 0);
-          G[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(aq[1], qh, G[b], 0, 0, 0);
-          G[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(aq[0], qh, G[b], 0, 0, 0);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    // staged reads done before the area is overwritten
-        __builtin_amdgcn_wave_barrier();
-      }
-    }
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      xf[ks][0] = xn[ks][0];
-      xf[ks][1] = xn[ks][1];
-    }
-  }
-  if (!MARGIN) fm_write_slab<NB>(G, racc, lossacc, r, h, lane, partial + (int64_t)slab * pstride);
+  fm_body<FmRowsF32, NB, LOSS, MARGIN>(X, n, ldx, y, sw, Wsp, sv, w0p, F, partial, pstride, nslab, slab0, margin);
 }
 
 // The two kernel families, as the host pass below takes them: the rows' element type and the
@@ -472,20 +342,12 @@ template <class FAM, int LOSS, bool MARGIN>
 int fm_launch(int nb, int grid, hipStream_t st, const typename FAM::elem* X, int64_t n, int64_t ldx, const float* y,
               const float* sw, const uint16_t* Wsp, const float* sv, const float* w0p, int F, float* partial,
               int pstride, int nslab, float* margin) {
-  // launches of `grid` blocks until every slab row has had its wave
-  for (int slab0 = 0; slab0 < nslab; slab0 += grid * kFmWaves) {
-    const int left = (nslab - slab0 + kFmWaves - 1) / kFmWaves, g = grid < left ? grid : left;
-    switch (nb) {
-#define O3S_FM(NBV) \
-  case NBV: hipLaunchKernelGGL((FAM::template kernel<NBV, LOSS, MARGIN>()), dim3(g), dim3(kFmThreads), 0, st, X, n, \
-                               ldx, y, sw, Wsp, sv, w0p, F, partial, pstride, nslab, slab0, margin); break;
-      O3S_FM(1) O3S_FM(2) O3S_FM(3) O3S_FM(4) O3S_FM(5) O3S_FM(6) O3S_FM(7) O3S_FM(8)
-#undef O3S_FM
-      default: return -1;
-    }
-    O3S_CHECK_LAUNCH();
-  }
-  return 0;
+  return mt_dispatch_nb(nb, [&](auto NB) {
+    return mt_walk_slabs(nslab, grid, kFmWaves, [&](int g, int slab0) {
+      hipLaunchKernelGGL((FAM::template kernel<NB, LOSS, MARGIN>()), dim3(g), dim3(kFmThreads), 0, st, X, n, ldx, y,
+                         sw, Wsp, sv, w0p, F, partial, pstride, nslab, slab0, margin);
+    });
+  });
 }
 
 // What the two pass entry points share: the argument check, the launch of the family's kernel

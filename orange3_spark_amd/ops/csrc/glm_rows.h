@@ -387,6 +387,11 @@ __device__ __forceinline__ uint32_t pk_bf16(float a, float b) {
   v[1] = b;
   return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, sm_bf16x2));
 }
+// Two fp32 -> two such dwords hi + lo: x - (hi + lo) is below 2^-17 |x|.
+__device__ __forceinline__ void split_bf16x2(float x0, float x1, uint32_t& ph, uint32_t& pl) {
+  ph = pk_bf16(x0, x1);
+  pl = pk_bf16(x0 - __uint_as_float(ph << 16), x1 - __uint_as_float(ph & 0xffff0000u));
+}
 // Two fp32 -> three such dwords hi + mid + lo, each the rounding of the exact remainder so
 // far: x - (hi + mid + lo) is below 2^-25 |x|, x - (hi + mid) below 2^-17 |x|.
 __device__ __forceinline__ void split_bf16x3(float x0, float x1, uint32_t& ph, uint32_t& pm, uint32_t& pl) {

@@ -6,43 +6,64 @@
 // Classification widget (orangecontrib/spark/widgets/ml/spark_ml_classification.py:15,
 // SURVEY §2.8 "Multinomial: X.W with C classes uses MFMA").
 //
-// Layout (v_mfma_f32_32x32x16_bf16; lane (r = lane&31, h = lane>>5)):
-//   forward  A = W split (32 classes x 16 dims, class r, dims 8h..+8), B = X (row r, the
-//            same 8 dims -- exactly the 16-B global load of the row) -> acc[v] = margin of
-//            row r, class 8(v>>2) + 4h + (v&3);
-//   backward A = R split (class r, rows 8h..+8 of a 16-row step), B = X^T (rows 8h..+8,
-//            dim r of a 32-dim block, read transposed from this wave's LDS copy of the
-//            tile) -> G[nb][v] = dG of class 8(v>>2) + 4h + (v&3), dim 32 nb + r.
-// X is exact in bf16; W is split into three bf16 terms (hi + mid + lo: margins and loss
-// at fp32 level), the residuals R (|R| <= w) into two (hi + lo: ~2^-17 relative per term
-// of the gradient sums).  The MFMA
-// work is a few % of the HBM time of a tile: the kernel streams X once per pass (the
-// next tile's rows are loaded while this tile computes).  One wave per SIMD (the
-// 128-register gradient accumulators); per-wave slab rows, summed in fp64 by
-// glm_finish_kernel (glm_launch.h) in a fixed order (no float atomics).
-// The two kernels share nothing with the binary GLM passes but that finish kernel and the
-// bf16 packing of glm_rows.h (pk_bf16, split_bf16x3).  Their differences from each other are
-// deliberate (see the budget note at the fp32 kernel); both sit at one wave per SIMD with no
-// scratch, which tools/isa_diff.py checks against the build before a change.
+// The tile, its lane layout and the term splitting are those of mfma_tile.h: W as three terms,
+// the residuals R (|R| <= w) as two.  The MFMA work is a few % of the HBM time of a tile: the
+// kernel streams X once per pass.  One wave per SIMD (the 128-register gradient accumulators);
+// per-wave slab rows [G class-major 32 x D | sum R (32) | loss].
+// The two kernels' differences from each other are deliberate (see the budget note at the fp32
+// kernel); both sit at one wave per SIMD with no scratch, which tools/isa_diff.py checks
+// against the build before a change.
 #include "glm_launch.h"
+#include "mfma_tile.h"
 
 namespace {
 
-typedef float sm_f32x16 __attribute__((ext_vector_type(16)));
-typedef short sm_bf16x8 __attribute__((ext_vector_type(8)));
 constexpr int kSmWaves = 4;
 constexpr int kSmThreads = kSmWaves * kWave;
 
 template <int NB>
-struct SmLds {
-  static constexpr int D = 32 * NB;
-  static constexpr int WLD = D + 8;     // +16 B per row: conflict-free 16-B fragment reads
-  static constexpr int XLD = D + 8;
-  static constexpr int RLD = 40;        // 80-B rows: the 16-B R fragment reads hit distinct banks
-  static constexpr int W_ELEMS = 3 * 32 * WLD;
-  static constexpr int WAVE_ELEMS = 32 * XLD + 2 * 32 * RLD;
+struct SmLds : MtPitch<NB> {
+  using P = MtPitch<NB>;
+  static constexpr int W_ELEMS = 3 * 32 * P::WLD;
+  static constexpr int WAVE_ELEMS = 32 * P::XLD + 2 * 32 * P::RLD;
   static constexpr int ELEMS = W_ELEMS + kSmWaves * WAVE_ELEMS;
 };
+
+// Label and weight of row `row` (-1 and 0 past n).
+__device__ __forceinline__ void sm_row(int64_t row, int64_t n, const int32_t* __restrict__ y,
+                                       const float* __restrict__ sw, int& yl, float& wr) {
+  const bool valid = row < n;
+  yl = valid ? y[row] : -1;
+  wr = valid ? (sw ? sw[row] : 1.f) : 0.f;
+}
+// Row log-sum-exp (the two half-waves hold disjoint class subsets of row r).
+__device__ __forceinline__ float sm_lse(const mt_f32x16 acc) {
+  float mx = -INFINITY;
+#pragma unroll
+  for (int v = 0; v < 16; ++v) mx = fmaxf(mx, acc[v]);
+  mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+  float se = 0.f;
+#pragma unroll
+  for (int v = 0; v < 16; ++v) se += __expf(acc[v] - mx);
+  se += __shfl_xor(se, 32, 64);
+  return mx + __logf(se);
+}
+// This wave's slab row: [G class-major 32 x D | sum R (32) | loss]
+template <int NB>
+__device__ __forceinline__ void sm_write_slab(const mt_f32x16 (&G)[NB], const float (&gb)[16], float lossacc,
+                                              float* out, int r, int h, int lane) {
+  constexpr int D = 32 * NB;
+  mt_write_slab_g<NB>(G, out, r, h);
+#pragma unroll
+  for (int v = 0; v < 16; ++v) {
+    float s = gb[v];
+#pragma unroll
+    for (int off = 16; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);   // over the 32 rows (same h)
+    if (r == 0) out[32 * D + 4 * h + mt_cv(v)] = s;
+  }
+  const float lt = wave_sum(lossacc);
+  if (lane == 0) out[32 * D + 32] = lt;
+}
 
 template <int NB>
 __global__ __launch_bounds__(kSmThreads, 1) void glm_softmax_kernel(
@@ -50,7 +71,7 @@ __global__ __launch_bounds__(kSmThreads, 1) void glm_softmax_kernel(
     const float* __restrict__ sw, const uint16_t* __restrict__ Wsp, const float* __restrict__ bias, int K,
     float* __restrict__ partial, int pstride) {
   using L = SmLds<NB>;
-  constexpr int D = L::D, KS = 2 * NB, WLD = L::WLD, XLD = L::XLD, RLD = L::RLD;
+  constexpr int KS = 2 * NB, WLD = L::WLD, XLD = L::XLD, RLD = L::RLD;
   __shared__ __attribute__((aligned(16))) uint16_t smem[L::ELEMS];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int r = lane & 31, h = lane >> 5;
@@ -58,22 +79,17 @@ __global__ __launch_bounds__(kSmThreads, 1) void glm_softmax_kernel(
   uint16_t* Xs = smem + L::W_ELEMS + wid * L::WAVE_ELEMS;
   uint16_t* Rs = Xs + 32 * XLD;
 
-  // W splits [3][32][D] -> LDS (padded rows)
-  for (int p = threadIdx.x; p < 3 * 32 * (D / 8); p += kSmThreads) {
-    const int row = p / (D / 8), k8 = p % (D / 8);
-    *reinterpret_cast<sm_bf16x8*>(Ws + row * WLD + k8 * 8) =
-        *reinterpret_cast<const sm_bf16x8*>(Wsp + (int64_t)row * D + k8 * 8);
-  }
+  mt_stage_w<3 * 32, NB, kSmThreads>(Ws, Wsp);
   float bl[16];
   int cls[16];
 #pragma unroll
   for (int v = 0; v < 16; ++v) {
-    cls[v] = 8 * (v >> 2) + 4 * h + (v & 3);
+    cls[v] = 4 * h + mt_cv(v);
     bl[v] = cls[v] < K ? bias[cls[v]] : -INFINITY;
   }
   __syncthreads();
 
-  sm_f32x16 G[NB];
+  mt_f32x16 G[NB];
 #pragma unroll
   for (int b = 0; b < NB; ++b)
 #pragma unroll
@@ -86,52 +102,26 @@ __global__ __launch_bounds__(kSmThreads, 1) void glm_softmax_kernel(
   const int64_t ntiles = (n + 31) / 32;
   const int64_t step = (int64_t)gridDim.x * kSmWaves;
   int64_t tile = (int64_t)blockIdx.x * kSmWaves + wid;
-  sm_bf16x8 xb[KS], xn[KS];
-  auto load = [&](int64_t t, sm_bf16x8 (&dst)[KS]) {
-    int64_t row = t * 32 + r;
-    row = row < n ? row : n - 1;
-    const uint16_t* src = X + row * ldx;
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      const int col = ks * 16 + 8 * h;
-      if (col < ldx) {
-        dst[ks] = *reinterpret_cast<const sm_bf16x8*>(src + col);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) dst[ks][j] = 0;
-      }
-    }
-  };
-  if (tile < ntiles) load(tile, xb);
+  mt_bf16x8 xb[KS], xn[KS];
+  if (tile < ntiles) mt_load_tile<MtBf16, KS>(X, n, ldx, tile, r, h, xb);
   for (; tile < ntiles; tile += step) {
-    if (tile + step < ntiles) load(tile + step, xn);
-    const int64_t row = tile * 32 + r;
-    const bool valid = row < n;
-    const int yl = valid ? y[row] : -1;
-    const float wr = valid ? (sw ? sw[row] : 1.f) : 0.f;
+    if (tile + step < ntiles) mt_load_tile<MtBf16, KS>(X, n, ldx, tile + step, r, h, xn);
+    int yl;
+    float wr;
+    sm_row(tile * 32 + r, n, y, sw, yl, wr);
     // ---- forward: margins of row r, 16 classes per lane
-    sm_f32x16 acc;
+    mt_f32x16 acc;
 #pragma unroll
     for (int v = 0; v < 16; ++v) acc[v] = bl[v];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
-#pragma unroll
-      for (int s = 0; s < 3; ++s) {
-        const sm_bf16x8 a = *reinterpret_cast<const sm_bf16x8*>(Ws + (s * 32 + r) * WLD + ks * 16 + 8 * h);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, xb[ks], acc, 0, 0, 0);
-      }
-      *reinterpret_cast<sm_bf16x8*>(Xs + r * XLD + ks * 16 + 8 * h) = xb[ks];   // for the X^T reads
+      const uint16_t* wp = Ws + r * WLD + ks * 16 + 8 * h;
+      acc = mt_mfma3(acc, *reinterpret_cast<const mt_bf16x8*>(wp), *reinterpret_cast<const mt_bf16x8*>(wp + 32 * WLD),
+                     *reinterpret_cast<const mt_bf16x8*>(wp + 64 * WLD), xb[ks]);
+      *reinterpret_cast<mt_bf16x8*>(Xs + r * XLD + ks * 16 + 8 * h) = xb[ks];   // for the X^T reads
     }
-    // ---- row softmax (the two half-waves hold disjoint class subsets of row r)
-    float mx = -INFINITY;
-#pragma unroll
-    for (int v = 0; v < 16; ++v) mx = fmaxf(mx, acc[v]);
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    float se = 0.f;
-#pragma unroll
-    for (int v = 0; v < 16; ++v) se += __expf(acc[v] - mx);
-    se += __shfl_xor(se, 32, 64);
-    const float lse = mx + __logf(se);
+    const float lse = sm_lse(acc);
+    // (the residual terms by integer rounding here, by v_cvt_pk_bf16_f32 in the fp32 kernel)
 #pragma unroll
     for (int v = 0; v < 16; ++v) {
       const bool hit = cls[v] == yl;
@@ -143,49 +133,29 @@ __global__ __launch_bounds__(kSmThreads, 1) void glm_softmax_kernel(
       Rs[(0 * 32 + cls[v]) * RLD + r] = a0;
       Rs[(1 * 32 + cls[v]) * RLD + r] = f32_to_bf16(rv - bf16_to_f32(a0));
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
+    mt_wave_sync();
     // ---- backward: G[class][dim] += sum over the tile's rows of R[row][class] X[row][dim]
-    sm_bf16x8 ar[2][2];
+    mt_bf16x8 ar[2][2];
 #pragma unroll
     for (int rs = 0; rs < 2; ++rs)
 #pragma unroll
       for (int s = 0; s < 2; ++s)
-        ar[rs][s] = *reinterpret_cast<const sm_bf16x8*>(Rs + (s * 32 + r) * RLD + rs * 16 + 8 * h);
+        ar[rs][s] = *reinterpret_cast<const mt_bf16x8*>(Rs + (s * 32 + r) * RLD + rs * 16 + 8 * h);
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
 #pragma unroll
       for (int rs = 0; rs < 2; ++rs) {
-        sm_bf16x8 bx;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) bx[q] = (short)Xs[(rs * 16 + 8 * h + q) * XLD + b * 32 + r];
+        const mt_bf16x8 bx = mt_read_xt(Xs, rs * 16 + 8 * h, b * 32 + r, XLD);
 #pragma unroll
         for (int s = 0; s < 2; ++s) G[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[rs][s], bx, G[b], 0, 0, 0);
       }
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    // tile's LDS reads done before it is overwritten
-    __builtin_amdgcn_wave_barrier();
+    mt_wave_sync();    // tile's LDS reads done before it is overwritten
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) xb[ks] = xn[ks];
   }
-  // ---- this wave's slab row: [G class-major 32 x D | sum R (32) | loss]
-  float* out = partial + ((int64_t)blockIdx.x * kSmWaves + wid) * pstride;
-#pragma unroll
-  for (int b = 0; b < NB; ++b)
-#pragma unroll
-    for (int v = 0; v < 16; ++v) out[cls[v] * D + b * 32 + r] = G[b][v];
-#pragma unroll
-  for (int v = 0; v < 16; ++v) {
-    float s = gb[v];
-#pragma unroll
-    for (int off = 16; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);   // over the 32 rows (same h)
-    if (r == 0) out[32 * D + cls[v]] = s;
-  }
-  const float lt = wave_sum(lossacc);
-  if (lane == 0) out[32 * D + 32] = lt;
+  sm_write_slab<NB>(G, gb, lossacc, partial + ((int64_t)blockIdx.x * kSmWaves + wid) * pstride, r, h, lane);
 }
-
-}  // namespace
 
 // ---------------------------------------------------------------------------------
 // Multinomial pass over fp32 rows: the contract, MFMA layouts, slab rows and finish of
@@ -195,9 +165,8 @@ __global__ __launch_bounds__(kSmThreads, 1) void glm_softmax_kernel(
 // split into bf16 terms as it is consumed (v_cvt_pk_bf16_f32 of the running remainder,
 // every subtraction exact): hi + mid + lo forward, where the margins and the loss have to
 // be at fp32 level, hi + mid backward (2^-17 relative, below the two-term split of R).
-// Forward products of total order <= 2 only (X hi with the three W terms, X mid with W hi
-// and mid, X lo with W hi: 6 MFMAs per 16 dims where the bf16 kernel issues 3); backward
-// all four of (R hi, R lo) x (X hi, X mid).
+// Forward products of total order <= 2 only (6 MFMAs per 16 dims where the bf16 kernel issues
+// 3); backward all four of (R hi, R lo) x (X hi, X mid).
 //
 // Budget.  An fp32 tile is twice the bytes of a bf16 one, so neither of the bf16 kernel's
 // two tile copies carries over: four 32-row hi + mid tiles and the W splits exceed the
@@ -214,36 +183,13 @@ __global__ __launch_bounds__(kSmThreads, 1) void glm_softmax_kernel(
 //     a lone wave per SIMD has; the bias lives in LDS and the class of an accumulator
 //     register is recomputed from the lane id so that the NB = 8 instantiation stays out
 //     of scratch (doc/performance.md has the table).
-// Chunks at or past ldx are zero-filled, rows past n are clamped and carry weight 0.
-namespace {
-
-typedef uint32_t sm_u32x4 __attribute__((ext_vector_type(4)));
-
-// 8 fp32 -> bf16 terms hi + mid + lo (split_bf16x3 of glm_rows.h, pair by pair).
-__device__ __forceinline__ void split8(const float4_ a, const float4_ b, sm_bf16x8& hi, sm_bf16x8& mid,
-                                       sm_bf16x8& lo) {
-  sm_u32x4 ph, pm, pl;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float x0 = j < 2 ? a[2 * j] : b[2 * j - 4], x1 = j < 2 ? a[2 * j + 1] : b[2 * j - 3];
-    uint32_t h, m, l;
-    split_bf16x3(x0, x1, h, m, l);
-    ph[j] = h;
-    pm[j] = m;
-    pl[j] = l;
-  }
-  hi = __builtin_bit_cast(sm_bf16x8, ph);
-  mid = __builtin_bit_cast(sm_bf16x8, pm);
-  lo = __builtin_bit_cast(sm_bf16x8, pl);
-}
-
 template <int NB>
 __global__ __launch_bounds__(kSmThreads, 1) void glm_softmax_f32_kernel(
     const float* __restrict__ X, int64_t n, int64_t ldx, const int32_t* __restrict__ y,
     const float* __restrict__ sw, const uint16_t* __restrict__ Wsp, const float* __restrict__ bias, int K,
     float* __restrict__ partial, int pstride) {
   using L = SmLds<NB>;
-  constexpr int D = L::D, KS = 2 * NB, WLD = L::WLD, XLD = L::XLD, RLD = L::RLD;
+  constexpr int KS = 2 * NB, WLD = L::WLD, XLD = L::XLD, RLD = L::RLD;
   __shared__ __attribute__((aligned(16))) uint16_t smem[L::ELEMS];
   __shared__ __attribute__((aligned(16))) float bs[32];   // bias, -inf for the classes past K
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -252,18 +198,12 @@ __global__ __launch_bounds__(kSmThreads, 1) void glm_softmax_f32_kernel(
   uint16_t* Xs = smem + L::W_ELEMS + wid * L::WAVE_ELEMS;   // [hi, mid][16 rows][XLD]
   uint16_t* Rs = Xs + 32 * XLD;
 
-  for (int p = threadIdx.x; p < 3 * 32 * (D / 8); p += kSmThreads) {
-    const int row = p / (D / 8), k8 = p % (D / 8);
-    *reinterpret_cast<sm_bf16x8*>(Ws + row * WLD + k8 * 8) =
-        *reinterpret_cast<const sm_bf16x8*>(Wsp + (int64_t)row * D + k8 * 8);
-  }
-  // register v of a lane's accumulator tile is class 4 h + cv(v)
-  auto cv = [](int v) { return 8 * (v >> 2) + (v & 3); };
+  mt_stage_w<3 * 32, NB, kSmThreads>(Ws, Wsp);
   if (threadIdx.x < 32) bs[threadIdx.x] = (int)threadIdx.x < K ? bias[threadIdx.x] : -INFINITY;
   uint16_t* Rw = Rs + 4 * h * RLD + r;
   __syncthreads();
 
-  sm_f32x16 G[NB];
+  mt_f32x16 G[NB];
 #pragma unroll
   for (int b = 0; b < NB; ++b)
 #pragma unroll
@@ -276,142 +216,77 @@ __global__ __launch_bounds__(kSmThreads, 1) void glm_softmax_f32_kernel(
   const int64_t ntiles = (n + 31) / 32;
   const int64_t step = (int64_t)gridDim.x * kSmWaves;
   int64_t tile = (int64_t)blockIdx.x * kSmWaves + wid;
-  float4_ xf[KS][2], xn[KS][2];
-  auto load = [&](int64_t t, float4_ (*dst)[2]) {
-    int64_t row = t * 32 + r;
-    row = row < n ? row : n - 1;
-    const float* src = X + row * ldx;
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      const int col = ks * 16 + 8 * h;
-      if (col < ldx) {
-        dst[ks][0] = *reinterpret_cast<const float4_*>(src + col);
-        dst[ks][1] = *reinterpret_cast<const float4_*>(src + col + 4);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) dst[ks][0][j] = dst[ks][1][j] = 0.f;
-      }
-    }
-  };
-  if (tile < ntiles) load(tile, xf);
+  MtF32::chunk xf[KS], xn[KS];
+  if (tile < ntiles) mt_load_tile<MtF32, KS>(X, n, ldx, tile, r, h, xf);
   for (; tile < ntiles; tile += step) {
-    if (tile + step < ntiles) load(tile + step, xn);
-    const int64_t row = tile * 32 + r;
-    const bool valid = row < n;
-    const int ylh = (valid ? y[row] : -1) - 4 * h;   // label relative to this half-wave's classes
-    const float wr = valid ? (sw ? sw[row] : 1.f) : 0.f;
+    if (tile + step < ntiles) mt_load_tile<MtF32, KS>(X, n, ldx, tile + step, r, h, xn);
+    int yl;
+    float wr;
+    sm_row(tile * 32 + r, n, y, sw, yl, wr);
+    const int ylh = yl - 4 * h;   // label relative to this half-wave's classes
     // ---- forward: margins of row r, 16 classes per lane; the hi and mid terms of the row
     // stay in the registers the fp32 values came in, for the backward staging below
-    sm_f32x16 acc;
+    mt_f32x16 acc;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const float4_ b4 = *reinterpret_cast<const float4_*>(bs + 8 * j + 4 * h);
 #pragma unroll
       for (int u = 0; u < 4; ++u) acc[4 * j + u] = b4[u];
     }
-    sm_bf16x8 xh[KS], xm[KS];
+    mt_bf16x8 xh[KS], xm[KS];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
-      sm_bf16x8 xl;
-      split8(xf[ks][0], xf[ks][1], xh[ks], xm[ks], xl);
+      mt_bf16x8 xl;
+      mt_split8(xf[ks].a, xf[ks].b, xh[ks], xm[ks], xl);
       const uint16_t* wp = Ws + r * WLD + ks * 16 + 8 * h;
-      const sm_bf16x8 a0 = *reinterpret_cast<const sm_bf16x8*>(wp);
-      const sm_bf16x8 a1 = *reinterpret_cast<const sm_bf16x8*>(wp + 32 * WLD);
-      const sm_bf16x8 a2 = *reinterpret_cast<const sm_bf16x8*>(wp + 64 * WLD);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, xl, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, xh[ks], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, xm[ks], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, xm[ks], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, xh[ks], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, xh[ks], acc, 0, 0, 0);
+      acc = mt_mfma6(acc, *reinterpret_cast<const mt_bf16x8*>(wp), *reinterpret_cast<const mt_bf16x8*>(wp + 32 * WLD),
+                     *reinterpret_cast<const mt_bf16x8*>(wp + 64 * WLD), xh[ks], xm[ks], xl);
       __builtin_amdgcn_sched_barrier(0);
     }
-    // ---- row softmax (the two half-waves hold disjoint class subsets of row r)
-    float mx = -INFINITY;
-#pragma unroll
-    for (int v = 0; v < 16; ++v) mx = fmaxf(mx, acc[v]);
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    float se = 0.f;
-#pragma unroll
-    for (int v = 0; v < 16; ++v) se += __expf(acc[v] - mx);
-    se += __shfl_xor(se, 32, 64);
-    const float lse = mx + __logf(se);
+    const float lse = sm_lse(acc);
 #pragma unroll
     for (int v = 0; v < 16; v += 2) {
       float rv[2];
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
-        const bool hit = cv(v + u) == ylh;
+        const bool hit = mt_cv(v + u) == ylh;
         rv[u] = wr * (__expf(acc[v + u] - lse) - (hit ? 1.f : 0.f));
         gb[v + u] += rv[u];
         if (hit) lossacc += wr * (lse - acc[v + u]);
       }
-      const uint32_t ph = pk_bf16(rv[0], rv[1]);
-      const uint32_t pl = pk_bf16(rv[0] - __uint_as_float(ph << 16), rv[1] - __uint_as_float(ph & 0xffff0000u));
-      Rw[cv(v) * RLD] = (uint16_t)ph;
-      Rw[cv(v + 1) * RLD] = (uint16_t)(ph >> 16);
-      Rw[(32 + cv(v)) * RLD] = (uint16_t)pl;
-      Rw[(32 + cv(v + 1)) * RLD] = (uint16_t)(pl >> 16);
+      mt_store_r_pair(Rw, v, rv[0], rv[1], RLD);
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
+    mt_wave_sync();
     // ---- backward: G[class][dim] += sum over the tile's rows of R[row][class] X[row][dim],
     // 16 rows (one MFMA k-step) at a time through this wave's staging area
-    sm_bf16x8 ar[2][2];
+    mt_bf16x8 ar[2][2];
 #pragma unroll
     for (int rs = 0; rs < 2; ++rs)
 #pragma unroll
       for (int s = 0; s < 2; ++s)
-        ar[rs][s] = *reinterpret_cast<const sm_bf16x8*>(Rs + (s * 32 + r) * RLD + rs * 16 + 8 * h);
+        ar[rs][s] = *reinterpret_cast<const mt_bf16x8*>(Rs + (s * 32 + r) * RLD + rs * 16 + 8 * h);
 #pragma unroll
     for (int rs = 0; rs < 2; ++rs) {
       if ((r >> 4) == rs) {
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
-          *reinterpret_cast<sm_bf16x8*>(Xs + (r & 15) * XLD + ks * 16 + 8 * h) = xh[ks];
-          *reinterpret_cast<sm_bf16x8*>(Xs + (16 + (r & 15)) * XLD + ks * 16 + 8 * h) = xm[ks];
+          *reinterpret_cast<mt_bf16x8*>(Xs + (r & 15) * XLD + ks * 16 + 8 * h) = xh[ks];
+          *reinterpret_cast<mt_bf16x8*>(Xs + (16 + (r & 15)) * XLD + ks * 16 + 8 * h) = xm[ks];
         }
       }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_wave_barrier();
+      mt_wave_sync();
 #pragma unroll
       for (int b = 0; b < NB; ++b) {
-        sm_bf16x8 bh, bm;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          bh[q] = (short)Xs[(8 * h + q) * XLD + b * 32 + r];
-          bm[q] = (short)Xs[(16 + 8 * h + q) * XLD + b * 32 + r];
-        }
-        G[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[rs][1], bm, G[b], 0, 0, 0);
-        G[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[rs][0], bm, G[b], 0, 0, 0);
-        G[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[rs][1], bh, G[b], 0, 0, 0);
-        G[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[rs][0], bh, G[b], 0, 0, 0);
+        const mt_bf16x8 bh = mt_read_xt(Xs, 8 * h, b * 32 + r, XLD), bm = mt_read_xt(Xs, 16 + 8 * h, b * 32 + r, XLD);
+        G[b] = mt_mfma4(G[b], ar[rs][0], ar[rs][1], bh, bm);
         __builtin_amdgcn_sched_barrier(0);
       }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    // staged reads done before the area is overwritten
-      __builtin_amdgcn_wave_barrier();
+      mt_wave_sync();    // staged reads done before the area is overwritten
     }
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      xf[ks][0] = xn[ks][0];
-      xf[ks][1] = xn[ks][1];
-    }
+    for (int ks = 0; ks < KS; ++ks) xf[ks] = xn[ks];
   }
-  // ---- this wave's slab row: [G class-major 32 x D | sum R (32) | loss]
-  float* out = partial + ((int64_t)blockIdx.x * kSmWaves + wid) * pstride;
-#pragma unroll
-  for (int b = 0; b < NB; ++b)
-#pragma unroll
-    for (int v = 0; v < 16; ++v) out[(4 * h + cv(v)) * D + b * 32 + r] = G[b][v];
-#pragma unroll
-  for (int v = 0; v < 16; ++v) {
-    float s = gb[v];
-#pragma unroll
-    for (int off = 16; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-    if (r == 0) out[32 * D + 4 * h + cv(v)] = s;
-  }
-  const float lt = wave_sum(lossacc);
-  if (lane == 0) out[32 * D + 32] = lt;
+  sm_write_slab<NB>(G, gb, lossacc, partial + ((int64_t)blockIdx.x * kSmWaves + wid) * pstride, r, h, lane);
 }
 
 // The two kernel families, as the host pass below takes them: the rows' element type and the
@@ -437,14 +312,11 @@ int softmax_pass(const void* X, int64_t n, int64_t ldx, int d, const int32_t* y,
   const auto* Xe = (const typename FAM::elem*)X;
   const uint16_t* Wh = (const uint16_t*)Wsp;
   if (n > 0) {
-    switch (nb) {
-#define O3S_SM(NBV) \
-  case NBV: hipLaunchKernelGGL(FAM::template kernel<NBV>(), dim3(grid), dim3(kSmThreads), 0, st, Xe, n, ldx, y, sw, \
-                               Wh, bias, K, partial, pstride); break;
-      O3S_SM(1) O3S_SM(2) O3S_SM(3) O3S_SM(4) O3S_SM(5) O3S_SM(6) O3S_SM(7) O3S_SM(8)
-#undef O3S_SM
-      default: return -1;
-    }
+    mt_dispatch_nb(nb, [&](auto NB) {
+      hipLaunchKernelGGL(FAM::template kernel<NB>(), dim3(grid), dim3(kSmThreads), 0, st, Xe, n, ldx, y, sw, Wh, bias,
+                         K, partial, pstride);
+      return 0;
+    });
   } else {
     hipMemsetAsync(partial, 0, sizeof(float) * pstride * (size_t)grid * kSmWaves, st);
   }

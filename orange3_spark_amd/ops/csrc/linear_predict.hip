@@ -5,14 +5,8 @@
 // (ops/linear_predict.py).  Reference: the `transform` of the fitted Spark models that the
 // Classification / PCA widgets apply (orangecontrib/spark/base/spark_ml_estimator.py).
 //
-// The tile is the forward half of glm_softmax_kernel (glm_softmax.hip), same operands:
-//   v_mfma_f32_32x32x16_bf16, lane (r = lane & 31, h = lane >> 5);
-//   A = W split (output r, dims 8h..+8 of a 16-dim step) from LDS, three bf16 terms hi + mid +
-//   lo; B = the row's own 16-B (bf16) / 32-B (fp32) global load (row r, the same 8 dims);
-//   acc[v] = output 8(v>>2) + 4h + (v&3) of row r.
-// bf16 rows are exact: 3 MFMAs per 16 dims.  fp32 rows are split as they are consumed into
-// hi + mid + lo (split_bf16x3) and only the products of total order <= 2 are formed: 6 MFMAs
-// per 16 dims.  Outputs are at fp32 level.  The bias comes as hi + lo floats: the
+// The tile is the forward half of mfma_tile.h: 3 MFMAs per 16 dims on bf16 rows, 6 on fp32
+// rows, outputs at fp32 level.  The bias comes as hi + lo floats: the
 // accumulators start from hi, lo is added after the products (a bernoulli NaiveBayes bias
 // reaches hundreds; one float would shift a whole class by its rounding).
 //
@@ -33,17 +27,13 @@
 // doubles, 1 KB contiguous per instruction.  With ldo != K (column blocks of a wider output)
 // or LP_DIRECT_STORE each lane stores its 32-B fragments itself.
 //
-// The next tile's rows are loaded while this one computes (plain vector loads into a second
-// register copy).  Without gradient accumulators the kernel holds two waves per SIMD; only
+// The rows are loaded non-temporally.  Without gradient accumulators the kernel holds two waves per SIMD; only
 // fp32 rows wider than 128 dims, whose two register copies alone are 256 VGPRs, stay at one
 // (doc/performance.md has the table; no instantiation uses scratch).
-#include "glm_rows.h"
+#include "mfma_tile.h"
 
 namespace {
 
-typedef float lp_f32x16 __attribute__((ext_vector_type(16)));
-typedef short lp_bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t lp_u32x4 __attribute__((ext_vector_type(4)));
 typedef double lp_f64x2 __attribute__((ext_vector_type(2)));
 constexpr int kLpWaves = 4;
 constexpr int kLpThreads = kLpWaves * kWave;
@@ -52,64 +42,25 @@ constexpr int kLpMaxLds = 160 * 1024;
 enum { LP_LOG_SOFTMAX_RAW = 1, LP_DIRECT_STORE = 2 };
 
 template <int NB>
-struct LpLds {
-  static constexpr int D = 32 * NB;
-  static constexpr int WLD = D + 8;      // +16 B per row: conflict-free 16-B fragment reads
-  static constexpr int W_ELEMS = 3 * 32 * WLD;
+struct LpLds : MtPitch<NB> {
+  static constexpr int W_ELEMS = 3 * 32 * MtPitch<NB>::WLD;
   static constexpr int BYTES = 2 * W_ELEMS + 4 * kLpWaves * kLpStage + 4 * 64;
 };
 
-// Row sources: the registers of one 16-dim step of a lane (dims 8h..+8 of row r), how they
-// are loaded and how they meet the three W terms a0 (hi), a1 (mid), a2 (lo).
-struct LpBf16 {
-  using elem = uint16_t;
-  struct chunk { lp_bf16x8 x; };
-  __device__ static __forceinline__ void load(const elem* p, chunk& c) {
-    c.x = __builtin_nontemporal_load(reinterpret_cast<const lp_bf16x8*>(p));
-  }
-  __device__ static __forceinline__ void zero(chunk& c) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) c.x[j] = 0;
-  }
-  __device__ static __forceinline__ void mma(const lp_bf16x8 a0, const lp_bf16x8 a1, const lp_bf16x8 a2,
-                                             const chunk& c, lp_f32x16& acc) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, c.x, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, c.x, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, c.x, acc, 0, 0, 0);
+// The row sources of mfma_tile.h and how a chunk meets the three W terms a0 (hi), a1 (mid),
+// a2 (lo), smallest terms first.
+struct LpBf16 : MtBf16 {
+  __device__ static __forceinline__ void mma(const mt_bf16x8 a0, const mt_bf16x8 a1, const mt_bf16x8 a2,
+                                             const chunk& c, mt_f32x16& acc) {
+    acc = mt_mfma3(acc, a2, a1, a0, c);
   }
 };
-struct LpF32 {
-  using elem = float;
-  struct chunk { float4_ a, b; };
-  __device__ static __forceinline__ void load(const elem* p, chunk& c) {
-    c.a = __builtin_nontemporal_load(reinterpret_cast<const float4_*>(p));
-    c.b = __builtin_nontemporal_load(reinterpret_cast<const float4_*>(p) + 1);
-  }
-  __device__ static __forceinline__ void zero(chunk& c) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) c.a[j] = c.b[j] = 0.f;
-  }
-  __device__ static __forceinline__ void mma(const lp_bf16x8 a0, const lp_bf16x8 a1, const lp_bf16x8 a2,
-                                             const chunk& c, lp_f32x16& acc) {
-    lp_u32x4 ph, pm, pl;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float x0 = j < 2 ? c.a[2 * j] : c.b[2 * j - 4], x1 = j < 2 ? c.a[2 * j + 1] : c.b[2 * j - 3];
-      uint32_t h, m, l;
-      split_bf16x3(x0, x1, h, m, l);
-      ph[j] = h;
-      pm[j] = m;
-      pl[j] = l;
-    }
-    const lp_bf16x8 xh = __builtin_bit_cast(lp_bf16x8, ph), xm = __builtin_bit_cast(lp_bf16x8, pm),
-                    xl = __builtin_bit_cast(lp_bf16x8, pl);
-    // smallest terms first: orders 2, 2, 2, then 1, 1, then 0
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, xl, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, xh, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, xm, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, xm, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, xh, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, xh, acc, 0, 0, 0);
+struct LpF32 : MtF32 {
+  __device__ static __forceinline__ void mma(const mt_bf16x8 a0, const mt_bf16x8 a1, const mt_bf16x8 a2,
+                                             const chunk& c, mt_f32x16& acc) {
+    mt_bf16x8 xh, xm, xl;
+    mt_split8(c.a, c.b, xh, xm, xl);
+    acc = mt_mfma6(acc, a0, a1, a2, xh, xm, xl);
   }
 };
 
@@ -126,7 +77,7 @@ __global__ __launch_bounds__(kLpThreads, (lp_min_blocks<SRC, NB>())) void linear
     double* __restrict__ raw, double* __restrict__ prob, double* __restrict__ pred, int64_t ldo) {
   using L = LpLds<NB>;
   using chunk = typename SRC::chunk;
-  constexpr int D = L::D, KS = 2 * NB, WLD = L::WLD;
+  constexpr int KS = 2 * NB, WLD = L::WLD;
   __shared__ __attribute__((aligned(16))) uint16_t Ws[L::W_ELEMS];
   __shared__ __attribute__((aligned(16))) float stage[kLpWaves * kLpStage];
   __shared__ __attribute__((aligned(16))) float bs[64];   // bias hi (-inf past K) | bias lo
@@ -134,12 +85,7 @@ __global__ __launch_bounds__(kLpThreads, (lp_min_blocks<SRC, NB>())) void linear
   const int r = lane & 31, h = lane >> 5;
   float* St = stage + wid * kLpStage;
 
-  // W splits [3][32][D] -> LDS (padded rows)
-  for (int p = threadIdx.x; p < 3 * 32 * (D / 8); p += kLpThreads) {
-    const int row = p / (D / 8), k8 = p % (D / 8);
-    *reinterpret_cast<lp_bf16x8*>(Ws + row * WLD + k8 * 8) =
-        *reinterpret_cast<const lp_bf16x8*>(Wsp + (int64_t)row * D + k8 * 8);
-  }
+  mt_stage_w<3 * 32, NB, kLpThreads>(Ws, Wsp);
   if (threadIdx.x < 32) {
     const bool in = (int)threadIdx.x < K;
     bs[threadIdx.x] = in ? bias_hi[threadIdx.x] : -INFINITY;
@@ -147,8 +93,6 @@ __global__ __launch_bounds__(kLpThreads, (lp_min_blocks<SRC, NB>())) void linear
   }
   __syncthreads();
 
-  // register v of a lane's accumulator tile is output 4 h + cv(v)
-  auto cv = [](int v) { return 8 * (v >> 2) + (v & 3); };
   const bool staged = ldo == K && !(flags & LP_DIRECT_STORE);
   const bool lsm = (flags & LP_LOG_SOFTMAX_RAW) != 0;
   const bool need_exp = prob != nullptr || (lsm && raw != nullptr);
@@ -157,29 +101,15 @@ __global__ __launch_bounds__(kLpThreads, (lp_min_blocks<SRC, NB>())) void linear
   const int64_t step = (int64_t)gridDim.x * kLpWaves;
   int64_t tile = (int64_t)blockIdx.x * kLpWaves + wid;
   chunk xb[KS], xn[KS];
-  auto load = [&](int64_t t, chunk (&dst)[KS]) {
-    int64_t row = t * 32 + r;
-    row = row < n ? row : n - 1;
-    const typename SRC::elem* src = X + row * ldx;
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      const int col = ks * 16 + 8 * h;
-      if (col < ldx) {
-        SRC::load(src + col, dst[ks]);
-      } else {
-        SRC::zero(dst[ks]);
-      }
-    }
-  };
-  if (tile < ntiles) load(tile, xb);
+  if (tile < ntiles) mt_load_tile<SRC, KS, true>(X, n, ldx, tile, r, h, xb);
   for (; tile < ntiles; tile += step) {
-    if (tile + step < ntiles) load(tile + step, xn);
+    if (tile + step < ntiles) mt_load_tile<SRC, KS, true>(X, n, ldx, tile + step, r, h, xn);
     const int64_t row0 = tile * 32, row = row0 + r;
     const bool valid = row < n;
     const int nrows = n - row0 < 32 ? (int)(n - row0) : 32;
 
     // ---- outputs of row r, 16 per lane
-    lp_f32x16 acc;
+    mt_f32x16 acc;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const float4_ b4 = *reinterpret_cast<const float4_*>(bs + 8 * j + 4 * h);
@@ -189,9 +119,9 @@ __global__ __launch_bounds__(kLpThreads, (lp_min_blocks<SRC, NB>())) void linear
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       const uint16_t* wp = Ws + r * WLD + ks * 16 + 8 * h;
-      const lp_bf16x8 a0 = *reinterpret_cast<const lp_bf16x8*>(wp);
-      const lp_bf16x8 a1 = *reinterpret_cast<const lp_bf16x8*>(wp + 32 * WLD);
-      const lp_bf16x8 a2 = *reinterpret_cast<const lp_bf16x8*>(wp + 64 * WLD);
+      const mt_bf16x8 a0 = *reinterpret_cast<const mt_bf16x8*>(wp);
+      const mt_bf16x8 a1 = *reinterpret_cast<const mt_bf16x8*>(wp + 32 * WLD);
+      const mt_bf16x8 a2 = *reinterpret_cast<const mt_bf16x8*>(wp + 64 * WLD);
       SRC::mma(a0, a1, a2, xb[ks], acc);
     }
 #pragma unroll
@@ -201,16 +131,15 @@ __global__ __launch_bounds__(kLpThreads, (lp_min_blocks<SRC, NB>())) void linear
       for (int u = 0; u < 4; ++u) acc[4 * j + u] += b4[u];
     }
 
-    // ---- one output matrix: vals[v] is output 4 h + cv(v) of row r
-    auto emit = [&](double* __restrict__ out, const lp_f32x16& vals) {
+    // ---- one output matrix: vals[v] is output 4 h + mt_cv(v) of row r
+    auto emit = [&](double* __restrict__ out, const mt_f32x16& vals) {
       if (staged) {
 #pragma unroll
         for (int v = 0; v < 16; ++v) {
-          const int c = 4 * h + cv(v);
+          const int c = 4 * h + mt_cv(v);
           if (c < K) St[r * K + c] = vals[v];
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_wave_barrier();
+        mt_wave_sync();
         const int E = nrows * K;
         double* base = out + row0 * K;
         for (int i = 2 * lane; i < E; i += 2 * kWave) {
@@ -224,13 +153,12 @@ __global__ __launch_bounds__(kLpThreads, (lp_min_blocks<SRC, NB>())) void linear
             base[i] = (double)St[i];
           }
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // staged reads done before the next overwrite
-        __builtin_amdgcn_wave_barrier();
+        mt_wave_sync();   // staged reads done before the next overwrite
       } else if (valid) {
         double* o = out + row * ldo + 4 * h;
 #pragma unroll
         for (int v = 0; v < 16; ++v) {
-          if (4 * h + cv(v) < K) o[cv(v)] = (double)vals[v];
+          if (4 * h + mt_cv(v) < K) o[mt_cv(v)] = (double)vals[v];
         }
       }
     };
@@ -242,7 +170,7 @@ __global__ __launch_bounds__(kLpThreads, (lp_min_blocks<SRC, NB>())) void linear
       for (int v = 1; v < 16; ++v) {
         const bool up = acc[v] > best;
         best = up ? acc[v] : best;
-        bi = up ? 4 * h + cv(v) : bi;
+        bi = up ? 4 * h + mt_cv(v) : bi;
       }
       const float ob = __shfl_xor(best, 32, 64);
       const int oi = __shfl_xor(bi, 32, 64);
@@ -254,7 +182,7 @@ __global__ __launch_bounds__(kLpThreads, (lp_min_blocks<SRC, NB>())) void linear
 #pragma unroll
       for (int v = 0; v < 16; ++v) mx = fmaxf(mx, acc[v]);
       mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-      lp_f32x16 e;
+      mt_f32x16 e;
       float se = 0.f;
 #pragma unroll
       for (int v = 0; v < 16; ++v) {
@@ -265,7 +193,7 @@ __global__ __launch_bounds__(kLpThreads, (lp_min_blocks<SRC, NB>())) void linear
       if (raw != nullptr) {
         if (lsm) {
           const float ls = logf(se);
-          lp_f32x16 t;
+          mt_f32x16 t;
 #pragma unroll
           for (int v = 0; v < 16; ++v) t[v] = (acc[v] - mx) - ls;
           emit(raw, t);
@@ -292,16 +220,12 @@ int lp_launch(const void* X, int64_t n, int64_t ldx, int nb, const void* Wsp, co
               int grid, hipStream_t st) {
   const auto* Xe = (const typename SRC::elem*)X;
   const uint16_t* Wh = (const uint16_t*)Wsp;
-  switch (nb) {
-#define O3S_LP(NBV) \
-  case NBV: hipLaunchKernelGGL((linear_predict_kernel<SRC, NBV>), dim3(grid), dim3(kLpThreads), 0, st, Xe, n, ldx, \
-                               Wh, bias_hi, bias_lo, K, flags, raw, prob, pred, ldo); break;
-    O3S_LP(1) O3S_LP(2) O3S_LP(3) O3S_LP(4) O3S_LP(5) O3S_LP(6) O3S_LP(7) O3S_LP(8)
-#undef O3S_LP
-    default: return -1;
-  }
-  O3S_CHECK_LAUNCH();
-  return 0;
+  return mt_dispatch_nb(nb, [&](auto NB) {
+    hipLaunchKernelGGL((linear_predict_kernel<SRC, NB>), dim3(grid), dim3(kLpThreads), 0, st, Xe, n, ldx, Wh, bias_hi,
+                       bias_lo, K, flags, raw, prob, pred, ldo);
+    O3S_CHECK_LAUNCH();
+    return 0;
+  });
 }
 
 constexpr int lp_lds_bytes(int nb) { return 2 * 3 * 32 * (32 * nb + 8) + 4 * kLpWaves * kLpStage + 4 * 64; }

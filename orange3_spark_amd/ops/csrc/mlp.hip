@@ -8,16 +8,10 @@
 // layer, softmax output with cross-entropy), reached from the classification widget.
 //
 // The pass is the multinomial pass of glm_softmax.hip with one more small MFMA layer in the
-// middle, and keeps that file's and fm.hip's structure: 32-row tiles,
-// v_mfma_f32_32x32x16_bf16 with lane (r = lane&31, h = lane>>5), the row's own global loads
-// as the forward B operand, the next tile prefetched into a second register copy, parameters
-// as hi + mid + lo bf16 terms, residual-like operands through LDS as hi + lo, slab rows summed
-// in fp64 by glm_finish_kernel in a fixed order.  No float atomics, and the same bits for any
-// grid.  Three-term operands meet in the six products of order <= 2; A and R stay in registers
-// between the layers and enter the next MFMA as three terms too (one more MFMA per k-step than
-// two terms, and the two-term remainder of R would reach gW1 through dH); the two-term
-// operands of the backward GEMMs meet in all four products, since lo x lo (2^-18) is as large
-// as what a two-term split leaves behind.
+// middle, on the tile and the term rules of mfma_tile.h; the same bits for any grid.  A and R
+// stay in registers between the layers and enter the next MFMA as three terms too (one more MFMA
+// per k-step than two terms, and the two-term remainder of R would reach gW1 through dH).  The
+// four products of the backward GEMMs are issued A term by A term here, not in mt_mfma4's order.
 //
 // Hidden blocks across the waves of a block.  H units are NH = ceil(H / 32) blocks of 32; the
 // gradient of W1 is H x D accumulators, one block of which fills a wave's registers at D = 256.
@@ -51,12 +45,9 @@
 //
 // A slab row (one per group of NH waves): [gW1 32 NH x D | gW2 32 x 32 NH | gb1 32 NH | gb2 32 | loss].
 #include "glm_launch.h"
+#include "mfma_tile.h"
 
 namespace {
-
-typedef float mlp_f32x16 __attribute__((ext_vector_type(16)));
-typedef short mlp_bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t mlp_u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kMlpMaxNh = 4, kMlpMaxNb = 8;
 // (NH, NB) the kernels are built for: up to NH NB = 16; on fp32 rows (twice the registers per row
@@ -67,11 +58,11 @@ constexpr bool mlp_taken(bool f32, int nh, int nb) {
 }
 
 template <int NH, int NB, bool F32, bool LOGITS>
-struct MlpLds {
-  static constexpr int D = 32 * NB;
-  static constexpr int WLD = D + 8;     // +16 B per row: conflict-free 16-B fragment reads
-  static constexpr int XLD = D + 8;
-  static constexpr int RLD = 40;        // 80-B rows: the 16-B fragment reads hit distinct banks
+struct MlpLds : MtPitch<NB> {
+  using MtPitch<NB>::D;
+  using MtPitch<NB>::WLD;
+  using MtPitch<NB>::XLD;
+  using MtPitch<NB>::RLD;
   static constexpr int FRAG = 64 * 8;   // one A fragment of a wave: 64 lanes x 16 B
   static constexpr int W1_ELEMS = 3 * 32 * NH * WLD;
   static constexpr int X_ELEMS = LOGITS ? 0 : (F32 ? 2 : 1) * 32 * XLD;
@@ -110,30 +101,28 @@ struct MlpLds {
   static_assert(BYTES <= 160 * 1024, "exceeds the LDS of a CU");
 };
 
-// register v of a lane's accumulator tile is class / unit 4 h + mlp_cv(v)
-__device__ __forceinline__ constexpr int mlp_cv(int v) { return 8 * (v >> 2) + (v & 3); }
-
 // 16 accumulator registers -> the B fragments of two k-steps (element e of k-step s is
 // register 8 s + e) as bf16 terms hi + mid (+ lo), each the rounding of the remainder so far.
-__device__ __forceinline__ void mlp_split16(const float (&x)[16], mlp_bf16x8 (&hi)[2], mlp_bf16x8 (&mid)[2]) {
+__device__ __forceinline__ void mlp_split16(const float (&x)[16], mt_bf16x8 (&hi)[2], mt_bf16x8 (&mid)[2]) {
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
-    mlp_u32x4 ph, pm;
+    mt_u32x4 ph, pm;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const float a = x[8 * s + 2 * j], b = x[8 * s + 2 * j + 1];
-      ph[j] = pk_bf16(a, b);
-      pm[j] = pk_bf16(a - __uint_as_float(ph[j] << 16), b - __uint_as_float(ph[j] & 0xffff0000u));
+      uint32_t h, m;
+      split_bf16x2(x[8 * s + 2 * j], x[8 * s + 2 * j + 1], h, m);
+      ph[j] = h;
+      pm[j] = m;
     }
-    hi[s] = __builtin_bit_cast(mlp_bf16x8, ph);
-    mid[s] = __builtin_bit_cast(mlp_bf16x8, pm);
+    hi[s] = __builtin_bit_cast(mt_bf16x8, ph);
+    mid[s] = __builtin_bit_cast(mt_bf16x8, pm);
   }
 }
-__device__ __forceinline__ void mlp_split16(const float (&x)[16], mlp_bf16x8 (&hi)[2], mlp_bf16x8 (&mid)[2],
-                                            mlp_bf16x8 (&lo)[2]) {
+__device__ __forceinline__ void mlp_split16(const float (&x)[16], mt_bf16x8 (&hi)[2], mt_bf16x8 (&mid)[2],
+                                            mt_bf16x8 (&lo)[2]) {
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
-    mlp_u32x4 ph, pm, pl;
+    mt_u32x4 ph, pm, pl;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       uint32_t h, m, l;
@@ -142,64 +131,24 @@ __device__ __forceinline__ void mlp_split16(const float (&x)[16], mlp_bf16x8 (&h
       pm[j] = m;
       pl[j] = l;
     }
-    hi[s] = __builtin_bit_cast(mlp_bf16x8, ph);
-    mid[s] = __builtin_bit_cast(mlp_bf16x8, pm);
-    lo[s] = __builtin_bit_cast(mlp_bf16x8, pl);
+    hi[s] = __builtin_bit_cast(mt_bf16x8, ph);
+    mid[s] = __builtin_bit_cast(mt_bf16x8, pm);
+    lo[s] = __builtin_bit_cast(mt_bf16x8, pl);
   }
-}
-
-// acc += W x for one k-step, W and x as hi + mid + lo terms: the six products of order <= 2,
-// small ones first.
-__device__ __forceinline__ mlp_f32x16 mlp_mfma6(mlp_f32x16 acc, const mlp_bf16x8 w0, const mlp_bf16x8 w1,
-                                                const mlp_bf16x8 w2, const mlp_bf16x8 x0, const mlp_bf16x8 x1,
-                                                const mlp_bf16x8 x2) {
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0, x2, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w2, x0, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w1, x1, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0, x1, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w1, x0, acc, 0, 0, 0);
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0, x0, acc, 0, 0, 0);
 }
 
 // The same two-term fragments -> LDS, class / unit major ([2][32][RLD], Bw = buffer + 4 h RLD + r),
 // for the A-operand (16 B along the rows) and transposed B-operand reads of the backward.
-__device__ __forceinline__ void mlp_store_t(const mlp_bf16x8 (&hi)[2], const mlp_bf16x8 (&lo)[2], uint16_t* Bw,
+__device__ __forceinline__ void mlp_store_t(const mt_bf16x8 (&hi)[2], const mt_bf16x8 (&lo)[2], uint16_t* Bw,
                                             int RLD) {
 #pragma unroll
   for (int s = 0; s < 2; ++s)
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      Bw[mlp_cv(8 * s + e) * RLD] = (uint16_t)hi[s][e];
-      Bw[(32 + mlp_cv(8 * s + e)) * RLD] = (uint16_t)lo[s][e];
+      Bw[mt_cv(8 * s + e) * RLD] = (uint16_t)hi[s][e];
+      Bw[(32 + mt_cv(8 * s + e)) * RLD] = (uint16_t)lo[s][e];
     }
 }
-
-// 8 fp32 -> bf16 terms hi + mid + lo (split_bf16x3 of glm_rows.h, pair by pair).
-__device__ __forceinline__ void mlp_split8(const float4_ a, const float4_ b, mlp_bf16x8& hi, mlp_bf16x8& mid,
-                                           mlp_bf16x8& lo) {
-  mlp_u32x4 ph, pm, pl;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float x0 = j < 2 ? a[2 * j] : b[2 * j - 4], x1 = j < 2 ? a[2 * j + 1] : b[2 * j - 3];
-    uint32_t h, m, l;
-    split_bf16x3(x0, x1, h, m, l);
-    ph[j] = h;
-    pm[j] = m;
-    pl[j] = l;
-  }
-  hi = __builtin_bit_cast(mlp_bf16x8, ph);
-  mid = __builtin_bit_cast(mlp_bf16x8, pm);
-  lo = __builtin_bit_cast(mlp_bf16x8, pl);
-}
-
-__device__ __forceinline__ void mlp_wave_sync() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_wave_barrier();
-}
-
-// The register copy of a tile row: 16 B (bf16) or 2 x 16 B (fp32) per 16 columns.
-template <bool F32> struct MlpChunk { mlp_bf16x8 v; };
-template <> struct MlpChunk<true> { float4_ a, b; };
 
 template <int NH, int NB, bool F32, bool LOGITS>
 __device__ __forceinline__ void mlp_body(const void* __restrict__ Xv, int64_t n, int64_t ldx,
@@ -208,7 +157,8 @@ __device__ __forceinline__ void mlp_body(const void* __restrict__ Xv, int64_t n,
                                          float* __restrict__ partial, int pstride, int nslab, int slab0,
                                          float* __restrict__ logits) {
   using L = MlpLds<NH, NB, F32, LOGITS>;
-  using elem = std::conditional_t<F32, float, uint16_t>;
+  using SRC = std::conditional_t<F32, MtF32, MtBf16>;
+  using elem = typename SRC::elem;
   constexpr int D = L::D, KS = 2 * NB, WLD = L::WLD, XLD = L::XLD, RLD = L::RLD, T = 64 * L::WAVES;
   __shared__ __attribute__((aligned(16))) uint16_t smem[L::ELEMS > 0 ? L::ELEMS : 8];
   __shared__ __attribute__((aligned(16))) float bs[L::BIAS_IN_LDS ? L::BIAS : 4];
@@ -227,14 +177,10 @@ __device__ __forceinline__ void mlp_body(const void* __restrict__ Xv, int64_t n,
   uint16_t* As = Rs + 2 * 32 * RLD;
 
   // W1 splits [3][32 NH][D] -> LDS (padded rows), the W2 fragments, the biases
-  for (int p = threadIdx.x; p < 3 * 32 * NH * (D / 8); p += T) {
-    const int row = p / (D / 8), k8 = p % (D / 8);
-    *reinterpret_cast<mlp_bf16x8*>(Ws + row * WLD + k8 * 8) =
-        *reinterpret_cast<const mlp_bf16x8*>(W1sp + (int64_t)row * D + k8 * 8);
-  }
+  mt_stage_w<3 * 32 * NH, NB, T>(Ws, W1sp);
   if constexpr (L::W2_IN_LDS) {
     for (int p = threadIdx.x; p < L::W2_ELEMS / 8; p += T)
-      *reinterpret_cast<mlp_bf16x8*>(W2s + p * 8) = *reinterpret_cast<const mlp_bf16x8*>(W2p + p * 8);
+      *reinterpret_cast<mt_bf16x8*>(W2s + p * 8) = *reinterpret_cast<const mt_bf16x8*>(W2p + p * 8);
   }
   if constexpr (L::BIAS_IN_LDS) {
     for (int p = threadIdx.x; p < L::BIAS; p += T) bs[p] = bias[p];
@@ -247,15 +193,15 @@ __device__ __forceinline__ void mlp_body(const void* __restrict__ Xv, int64_t n,
     }
   };
   // fragment t (hi, mid, lo) of k-step s of W2 (which = 0) or W2^T (which = 1) for this wave's block
-  mlp_bf16x8 w2r[L::W2_IN_LDS ? 1 : (LOGITS ? 6 : 12)];
+  mt_bf16x8 w2r[L::W2_IN_LDS ? 1 : (LOGITS ? 6 : 12)];
   if constexpr (!L::W2_IN_LDS) {
 #pragma unroll
     for (int i = 0; i < (LOGITS ? 6 : 12); ++i)
-      w2r[i] = *reinterpret_cast<const mlp_bf16x8*>(W2p + ((((i / 6) * NH + wid) * 6 + i % 6) * 64 + lane) * 8);
+      w2r[i] = *reinterpret_cast<const mt_bf16x8*>(W2p + ((((i / 6) * NH + wid) * 6 + i % 6) * 64 + lane) * 8);
   }
-  auto w2frag = [&](int which, int s, int t) -> mlp_bf16x8 {
+  auto w2frag = [&](int which, int s, int t) -> mt_bf16x8 {
     if constexpr (L::W2_IN_LDS) {
-      return *reinterpret_cast<const mlp_bf16x8*>(W2s + (((which * NH + wid) * 6 + s * 3 + t) * 64 + lane) * 8);
+      return *reinterpret_cast<const mt_bf16x8*>(W2s + (((which * NH + wid) * 6 + s * 3 + t) * 64 + lane) * 8);
     } else {
       return w2r[which * 6 + s * 3 + t];
     }
@@ -271,7 +217,7 @@ __device__ __forceinline__ void mlp_body(const void* __restrict__ Xv, int64_t n,
   int64_t tile = LOGITS ? (int64_t)blockIdx.x * L::GROUPS + grp : (int64_t)slab;
   if (!LOGITS && slab >= nslab) return;   // the whole group: with NH > 1 the block, else an independent wave
 
-  mlp_f32x16 G[NB], G2;
+  mt_f32x16 G[NB], G2;
   float gb1[16], gb2[16], lossacc = 0.f;
 #pragma unroll
   for (int v = 0; v < 16; ++v) {
@@ -286,63 +232,36 @@ __device__ __forceinline__ void mlp_body(const void* __restrict__ Xv, int64_t n,
     for (int v = 0; v < 32; ++v) gbl[v * 64] = 0.f;
   }
 
-  MlpChunk<F32> xc[KS], xn[KS];
-  auto load = [&](int64_t t, MlpChunk<F32> (&dst)[KS]) {
-    int64_t row = t * 32 + r;
-    row = row < n ? row : n - 1;
-    const elem* src = X + row * ldx;
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      const int col = ks * 16 + 8 * h;
-      if constexpr (F32) {
-        if (col < ldx) {
-          dst[ks].a = *reinterpret_cast<const float4_*>(src + col);
-          dst[ks].b = *reinterpret_cast<const float4_*>(src + col + 4);
-        } else {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) dst[ks].a[j] = dst[ks].b[j] = 0.f;
-        }
-      } else {
-        if (col < ldx) {
-          dst[ks].v = *reinterpret_cast<const mlp_bf16x8*>(src + col);
-        } else {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) dst[ks].v[j] = 0;
-        }
-      }
-    }
-  };
-  if (tile < ntiles) load(tile, xc);
+  typename SRC::chunk xc[KS], xn[KS];
+  if (tile < ntiles) mt_load_tile<SRC, KS>(X, n, ldx, tile, r, h, xc);
   for (; tile < ntiles; tile += step) {
-    if (tile + step < ntiles) load(tile + step, xn);
+    if (tile + step < ntiles) mt_load_tile<SRC, KS>(X, n, ldx, tile + step, r, h, xn);
     const int64_t row = tile * 32 + r;
     const bool valid = row < n;
     // ---- hidden layer: Z of row r, 16 units of this wave's block per lane.  On fp32 rows the
     // hi and mid terms stay in registers for the shared tile
-    mlp_f32x16 z;
+    mt_f32x16 z;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const float4_ b4 = bias4(32 * wid + 8 * q + 4 * h);
 #pragma unroll
       for (int u = 0; u < 4; ++u) z[4 * q + u] = b4[u];
     }
-    mlp_bf16x8 xh[KS], xm[F32 ? KS : 1];
+    mt_bf16x8 xh[KS], xm[F32 ? KS : 1];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       const uint16_t* wp = Ws + (32 * wid + r) * WLD + ks * 16 + 8 * h;
-      const mlp_bf16x8 a0 = *reinterpret_cast<const mlp_bf16x8*>(wp);
-      const mlp_bf16x8 a1 = *reinterpret_cast<const mlp_bf16x8*>(wp + 32 * NH * WLD);
-      const mlp_bf16x8 a2 = *reinterpret_cast<const mlp_bf16x8*>(wp + 64 * NH * WLD);
+      const mt_bf16x8 a0 = *reinterpret_cast<const mt_bf16x8*>(wp);
+      const mt_bf16x8 a1 = *reinterpret_cast<const mt_bf16x8*>(wp + 32 * NH * WLD);
+      const mt_bf16x8 a2 = *reinterpret_cast<const mt_bf16x8*>(wp + 64 * NH * WLD);
       if constexpr (F32) {
-        mlp_bf16x8 xl;
-        mlp_split8(xc[ks].a, xc[ks].b, xh[ks], xm[ks], xl);
-        z = mlp_mfma6(z, a0, a1, a2, xh[ks], xm[ks], xl);
+        mt_bf16x8 xl;
+        mt_split8(xc[ks].a, xc[ks].b, xh[ks], xm[ks], xl);
+        z = mt_mfma6(z, a0, a1, a2, xh[ks], xm[ks], xl);
         __builtin_amdgcn_sched_barrier(0);
       } else {
-        xh[ks] = xc[ks].v;
-        z = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, xh[ks], z, 0, 0, 0);
-        z = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, xh[ks], z, 0, 0, 0);
-        z = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, xh[ks], z, 0, 0, 0);
+        xh[ks] = xc[ks];
+        z = mt_mfma3(z, a2, a1, a0, xh[ks]);
       }
     }
     float a[16];
@@ -352,23 +271,23 @@ __device__ __forceinline__ void mlp_body(const void* __restrict__ Xv, int64_t n,
 #pragma unroll
       for (int u = 0; u < 4; ++u) a[4 * q + u] = 1.f / (1.f + __expf(-(z[4 * q + u] + b4[u])));
     }
-    mlp_bf16x8 ah[2], am[2], al[2];
+    mt_bf16x8 ah[2], am[2], al[2];
     mlp_split16(a, ah, am, al);
     // ---- output layer: this block's share of the logits of row r, 16 classes per lane
-    mlp_f32x16 lg;
+    mt_f32x16 lg;
 #pragma unroll
     for (int v = 0; v < 16; ++v) lg[v] = 0.f;
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      lg = mlp_mfma6(lg, w2frag(0, s, 0), w2frag(0, s, 1), w2frag(0, s, 2), ah[s], am[s], al[s]);
+      lg = mt_mfma6(lg, w2frag(0, s, 0), w2frag(0, s, 1), w2frag(0, s, 2), ah[s], am[s], al[s]);
     }
     auto share_x = [&]() {   // this wave's k-steps of the tile -> the block's X tile
       if constexpr (!LOGITS) {
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
           if (NH == 1 || ks % NH == wid) {
-            *reinterpret_cast<mlp_bf16x8*>(Xs + r * XLD + ks * 16 + 8 * h) = xh[ks];
-            if constexpr (F32) *reinterpret_cast<mlp_bf16x8*>(Xs + (32 + r) * XLD + ks * 16 + 8 * h) = xm[ks];
+            *reinterpret_cast<mt_bf16x8*>(Xs + r * XLD + ks * 16 + 8 * h) = xh[ks];
+            if constexpr (F32) *reinterpret_cast<mt_bf16x8*>(Xs + (32 + r) * XLD + ks * 16 + 8 * h) = xm[ks];
           }
         }
       }
@@ -434,23 +353,23 @@ __device__ __forceinline__ void mlp_body(const void* __restrict__ Xv, int64_t n,
       float rv[16];
 #pragma unroll
       for (int v = 0; v < 16; ++v) {
-        const bool hit = mlp_cv(v) == ylh;
+        const bool hit = mt_cv(v) == ylh;
         rv[v] = valid ? __expf(lg[v] - lse) - (hit ? 1.f : 0.f) : 0.f;
         if constexpr (L::GB_IN_LDS) gbl[v * 64] += rv[v]; else gb2[v] += rv[v];
         if (hit) lossacc += lse - lg[v];
       }
-      mlp_bf16x8 rh[2], rm[2], rl[2];
+      mt_bf16x8 rh[2], rm[2], rl[2];
       mlp_split16(rv, rh, rm, rl);
       mlp_store_t(rh, rm, Rs + 4 * h * RLD + r, RLD);
       mlp_store_t(ah, am, As + 4 * h * RLD + r, RLD);
       // ---- dH = W2 R in the layout of A, dZ in-lane.  Classes 16..31 are k-step 1
-      mlp_f32x16 dh;
+      mt_f32x16 dh;
 #pragma unroll
       for (int v = 0; v < 16; ++v) dh[v] = 0.f;
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
         if (s == 0 || K > 16)
-          dh = mlp_mfma6(dh, w2frag(1, s, 0), w2frag(1, s, 1), w2frag(1, s, 2), rh[s], rm[s], rl[s]);
+          dh = mt_mfma6(dh, w2frag(1, s, 0), w2frag(1, s, 1), w2frag(1, s, 2), rh[s], rm[s], rl[s]);
       }
       float dz[16];
 #pragma unroll
@@ -458,43 +377,39 @@ __device__ __forceinline__ void mlp_body(const void* __restrict__ Xv, int64_t n,
         dz[v] = dh[v] * (a[v] * (1.f - a[v]));
         if constexpr (L::GB_IN_LDS) gbl[(16 + v) * 64] += dz[v]; else gb1[v] += dz[v];
       }
-      mlp_wave_sync();
+      mt_wave_sync();
       // ---- gW2[class][unit] += sum over the tile's rows of R[row][class] A[row][unit]
 #pragma unroll
       for (int rs = 0; rs < 2; ++rs) {
         const int o = r * RLD + rs * 16 + 8 * h;
-        const mlp_bf16x8 ar0 = *reinterpret_cast<const mlp_bf16x8*>(Rs + o);
-        const mlp_bf16x8 ar1 = *reinterpret_cast<const mlp_bf16x8*>(Rs + 32 * RLD + o);
-        const mlp_bf16x8 ba0 = *reinterpret_cast<const mlp_bf16x8*>(As + o);
-        const mlp_bf16x8 ba1 = *reinterpret_cast<const mlp_bf16x8*>(As + 32 * RLD + o);
+        const mt_bf16x8 ar0 = *reinterpret_cast<const mt_bf16x8*>(Rs + o);
+        const mt_bf16x8 ar1 = *reinterpret_cast<const mt_bf16x8*>(Rs + 32 * RLD + o);
+        const mt_bf16x8 ba0 = *reinterpret_cast<const mt_bf16x8*>(As + o);
+        const mt_bf16x8 ba1 = *reinterpret_cast<const mt_bf16x8*>(As + 32 * RLD + o);
         G2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar1, ba1, G2, 0, 0, 0);
         G2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar1, ba0, G2, 0, 0, 0);
         G2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar0, ba1, G2, 0, 0, 0);
         G2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar0, ba0, G2, 0, 0, 0);
       }
-      mlp_wave_sync();    // R has been read: dZ takes its buffer
-      mlp_bf16x8 dzh[2], dzl[2];
+      mt_wave_sync();    // R has been read: dZ takes its buffer
+      mt_bf16x8 dzh[2], dzl[2];
       mlp_split16(dz, dzh, dzl);
       mlp_store_t(dzh, dzl, Rs + 4 * h * RLD + r, RLD);
-      mlp_wave_sync();
+      mt_wave_sync();
       // ---- gW1[unit][dim] += sum over the tile's rows of dZ[row][unit] X[row][dim]
-      mlp_bf16x8 ad[2][2];
+      mt_bf16x8 ad[2][2];
 #pragma unroll
       for (int rs = 0; rs < 2; ++rs)
 #pragma unroll
         for (int s = 0; s < 2; ++s)
-          ad[rs][s] = *reinterpret_cast<const mlp_bf16x8*>(Rs + (s * 32 + r) * RLD + rs * 16 + 8 * h);
+          ad[rs][s] = *reinterpret_cast<const mt_bf16x8*>(Rs + (s * 32 + r) * RLD + rs * 16 + 8 * h);
 #pragma unroll
       for (int b = 0; b < NB; ++b) {
 #pragma unroll
         for (int rs = 0; rs < 2; ++rs) {
-          mlp_bf16x8 bx;
-#pragma unroll
-          for (int q = 0; q < 8; ++q) bx[q] = (short)Xs[(rs * 16 + 8 * h + q) * XLD + b * 32 + r];
+          const mt_bf16x8 bx = mt_read_xt(Xs, rs * 16 + 8 * h, b * 32 + r, XLD);
           if constexpr (F32) {
-            mlp_bf16x8 bm;
-#pragma unroll
-            for (int q = 0; q < 8; ++q) bm[q] = (short)Xs[(32 + rs * 16 + 8 * h + q) * XLD + b * 32 + r];
+            const mt_bf16x8 bm = mt_read_xt(Xs, 32 + rs * 16 + 8 * h, b * 32 + r, XLD);
             G[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ad[rs][1], bm, G[b], 0, 0, 0);
             G[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ad[rs][1], bx, G[b], 0, 0, 0);
             G[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ad[rs][0], bm, G[b], 0, 0, 0);
@@ -505,7 +420,7 @@ __device__ __forceinline__ void mlp_body(const void* __restrict__ Xv, int64_t n,
           }
         }
       }
-      mlp_wave_sync();    // this tile's LDS reads are done before the wave writes the next one's
+      mt_wave_sync();    // this tile's LDS reads are done before the wave writes the next one's
     }
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) xc[ks] = xn[ks];
@@ -516,11 +431,10 @@ __device__ __forceinline__ void mlp_body(const void* __restrict__ Xv, int64_t n,
     float* o2 = out + 32 * NH * D;
     float* o3 = o2 + 32 * 32 * NH;
     float* o4 = o3 + 32 * NH;
+    mt_write_slab_g<NB>(G, out + 32 * wid * D, r, h);
 #pragma unroll
     for (int v = 0; v < 16; ++v) {
-      const int c = 4 * h + mlp_cv(v);
-#pragma unroll
-      for (int b = 0; b < NB; ++b) out[(32 * wid + c) * D + b * 32 + r] = G[b][v];
+      const int c = 4 * h + mt_cv(v);
       o2[c * 32 * NH + 32 * wid + r] = G2[v];
       float s1 = gb1[v], s2 = gb2[v];
       if constexpr (L::GB_IN_LDS) {
@@ -583,37 +497,34 @@ int mlp_launch_inst(int grid, hipStream_t st, const typename MlpFam<F32>::elem* 
                     float* partial, int pstride, int nslab, float* logits) {
   using L = MlpLds<NH, NB, F32, LOGITS>;
   const auto kernel = MlpFam<F32>::template kernel<NH, NB, LOGITS>();
-  const int64_t ntiles = (n + 31) / 32;
-  const int64_t walks = LOGITS ? ntiles : (int64_t)nslab;
-  for (int64_t w0 = 0; w0 < walks; w0 += (int64_t)grid * L::GROUPS) {
-    const int64_t left = (walks - w0 + L::GROUPS - 1) / L::GROUPS;
-    const int g = (int)(grid < left ? grid : left);
+  // logits: a grid-stride walk covers every tile in one launch of at most `grid` blocks
+  const int64_t ntiles = (n + 31) / 32, reach = (int64_t)grid * L::GROUPS;
+  const int64_t walks = LOGITS ? (ntiles < reach ? ntiles : reach) : (int64_t)nslab;
+  return mt_walk_slabs(walks, grid, L::GROUPS, [&](int g, int w0) {
     hipLaunchKernelGGL(kernel, dim3(g), dim3(64 * L::WAVES), 0, st, X, n, ldx, y, W1sp, W2p, bias, K, partial,
-                       pstride, nslab, (int)w0, logits);
-    O3S_CHECK_LAUNCH();
-    if (LOGITS) break;   // a grid-stride walk covers every tile
-  }
-  return 0;
+                       pstride, nslab, w0, logits);
+  });
 }
 
 template <bool F32, bool LOGITS>
 int mlp_launch(int nh, int nb, int grid, hipStream_t st, const typename MlpFam<F32>::elem* X, int64_t n, int64_t ldx,
                const int32_t* y, const uint16_t* W1sp, const uint16_t* W2p, const float* bias, int K, float* partial,
                int pstride, int nslab, float* logits) {
-#define O3S_MLP(NHV, NBV)                                                                                       \
-  if (nh == NHV && nb == NBV) {                                                                                 \
-    if constexpr (mlp_taken(F32, NHV, NBV))                                                                     \
-      return mlp_launch_inst<NHV, NBV, F32, LOGITS>(grid, st, X, n, ldx, y, W1sp, W2p, bias, K, partial, pstride, \
-                                                    nslab, logits);                                             \
-    return -1;                                                                                                  \
+  const auto leg = [&](auto NH) {
+    return mt_dispatch_nb(nb, [&](auto NB) {
+      if constexpr (mlp_taken(F32, NH, NB))
+        return mlp_launch_inst<NH, NB, F32, LOGITS>(grid, st, X, n, ldx, y, W1sp, W2p, bias, K, partial, pstride,
+                                                    nslab, logits);
+      return -1;
+    });
+  };
+  switch (nh) {
+    case 1: return leg(IC<1>{});
+    case 2: return leg(IC<2>{});
+    case 3: return leg(IC<3>{});
+    case 4: return leg(IC<4>{});
+    default: return -1;
   }
-#define O3S_MLP_ROW(NHV) \
-  O3S_MLP(NHV, 1) O3S_MLP(NHV, 2) O3S_MLP(NHV, 3) O3S_MLP(NHV, 4) O3S_MLP(NHV, 5) O3S_MLP(NHV, 6) O3S_MLP(NHV, 7) \
-  O3S_MLP(NHV, 8)
-  O3S_MLP_ROW(1) O3S_MLP_ROW(2) O3S_MLP_ROW(3) O3S_MLP_ROW(4)
-#undef O3S_MLP_ROW
-#undef O3S_MLP
-  return -1;
 }
 
 // What the two pass entry points share: the argument check, the launches (an empty pass zeroes

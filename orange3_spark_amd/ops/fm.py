@@ -19,6 +19,7 @@ import os
 import torch
 
 from . import _native as N
+from ._terms import hi_lo, pad_rows, split3
 from .glm import LOSS_LOGISTIC, LOSS_SQUARED
 
 MAX_D = 256      # columns of a row the kernels take
@@ -61,10 +62,7 @@ def _check_loss(loss: int) -> int:
 
 
 def _operands(X: torch.Tensor, V: torch.Tensor, w: torch.Tensor, w0):
-    """The kernel operands, built on the device (no host sync): the hi + mid + lo bf16 split
-    of the class-major ``[V^T | w]`` padded to [32, D], ``s`` as fp32 [D], ``w0`` as hi + lo
-    floats, and the fp64 ``V`` the gradient is assembled with.  ``V`` and ``w`` enter at
-    fp32."""
+    """The checked sizes ``(d, F)`` and the :func:`_pack` of the model on the rows' device."""
     d = X.shape[1]
     F = V.shape[1]
     if V.shape[0] != d or w.shape[0] != d:
@@ -72,24 +70,23 @@ def _operands(X: torch.Tensor, V: torch.Tensor, w: torch.Tensor, w0):
     if not fm_kernel_ok(X, F):
         raise ValueError("FM kernel rows must be CUDA bf16 / fp32 with unit column stride, a row stride that is "
                          f"a multiple of 8, at most {MAX_D} columns, and 1 <= F <= {MAX_F}")
-    dev = X.device
+    return (d, F) + _pack(V, w, w0, X.device)
+
+
+def _pack(V: torch.Tensor, w: torch.Tensor, w0, dev):
+    """The kernel operands ``(D, Wsp, sv, w0p, V64)``, built on the device (no host sync): the
+    hi + mid + lo bf16 split of the class-major ``[V^T | w]`` padded to [32, D], ``s`` as fp32
+    [D], ``w0`` as hi + lo floats, and the fp64 ``V`` the gradient is assembled with.  ``V`` and
+    ``w`` enter at fp32."""
+    d = V.shape[0]
     D = 32 * (-(-d // 32))
     V32 = V.to(dev, torch.float32)
-    Wp = torch.zeros((32, D), dtype=torch.float32, device=dev)
-    Wp[:F, :d] = V32.T
-    Wp[F, :d] = w.to(dev, torch.float32)
-    hi = Wp.to(torch.bfloat16)
-    r1 = Wp - hi.float()
-    mid = r1.to(torch.bfloat16)
-    lo = (r1 - mid.float()).to(torch.bfloat16)
-    Wsp = torch.stack([hi, mid, lo]).contiguous()
+    Wsp = split3(pad_rows(torch.cat([V32.T, w.to(dev, torch.float32)[None]]), 32, D)).contiguous()
     V64 = V32.double()
     sv = torch.zeros(D, dtype=torch.float32, device=dev)
     sv[:d] = (V64 * V64).sum(1).float()
-    w064 = _w0_f64(w0, dev)
-    w0h = w064.float()
-    w0p = torch.stack([w0h, (w064 - w0h.double()).float()]).contiguous()
-    return d, F, D, Wsp, sv, w0p, V64
+    w0p = torch.stack(hi_lo(_w0_f64(w0, dev))).contiguous()
+    return D, Wsp, sv, w0p, V64
 
 
 def fm_pass(X: torch.Tensor, y: torch.Tensor, sw: torch.Tensor | None, V: torch.Tensor, w: torch.Tensor, w0,

@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from ._terms import pad_rows, split3
 
 LOSS_LOGISTIC, LOSS_HINGE, LOSS_SQUARED = 0, 1, 2
 log = logging.getLogger(__name__)
@@ -584,16 +585,7 @@ def softmax_pass(X: torch.Tensor, y: torch.Tensor, sw: torch.Tensor | None, W: t
     n, d = X.shape
     K = W.shape[0]
     dev = X.device
-    D = 32 * (-(-d // 32))
-    Wp = torch.zeros((32, D), dtype=torch.float32, device=dev)
-    Wp[:K, :d] = W
-    hi = Wp.to(torch.bfloat16)
-    r1 = Wp - hi.float()
-    mid = r1.to(torch.bfloat16)
-    lo = (r1 - mid.float()).to(torch.bfloat16)
-    Wsp = torch.stack([hi, mid, lo]).contiguous()
-    bp = torch.zeros(32, dtype=torch.float32, device=dev)
-    bp[:K] = b
+    D, Wsp, bp = softmax_operands(W, b, dev)
     grid = N.num_cus(dev)
     pstride = 32 * D + 33
     partial = torch.empty(grid * 4 * pstride, dtype=torch.float32, device=dev)
@@ -606,6 +598,14 @@ def softmax_pass(X: torch.Tensor, y: torch.Tensor, sw: torch.Tensor | None, W: t
                Wsp.data_ptr(), bp.data_ptr(), K, partial.data_ptr(), grid,
                out.data_ptr(), N.stream_of(X)), "glm_softmax")
     return out[: 32 * D].view(32, D)[:K, :d], out[32 * D:32 * D + K], out[32 * D + 32]
+
+
+def softmax_operands(W: torch.Tensor, b: torch.Tensor, dev):
+    """``(D, Wsp [3, 32, D] bf16 terms of the padded W, bp [32] fp32 padded bias)`` on ``dev``."""
+    D = 32 * (-(-W.shape[1] // 32))
+    bp = torch.zeros(32, dtype=torch.float32, device=dev)
+    bp[:W.shape[0]] = b
+    return D, split3(pad_rows(W.to(dev), 32, D)).contiguous(), bp
 
 
 def softmax_pass_torch(X, y, sw, W, b):

@@ -12,6 +12,7 @@ import torch
 
 from . import _native as N
 from . import glm as G
+from ._terms import hi_lo, pad_rows, split3
 
 MAX_D = 256                          # logical columns of a row the kernel takes
 MAX_K = 32                           # outputs of one launch
@@ -116,19 +117,12 @@ def pack(W, b=None) -> PackedLinear:
     if b.shape[0] != K:
         raise ValueError(f"bias has {b.shape[0]} entries for {K} outputs")
     nblk, D = -(-K // MAX_K), 32 * (-(-d // 32))
-    Wp = torch.zeros((nblk * MAX_K, D), dtype=torch.float32)
-    Wp[:K, :d] = torch.from_numpy(W).to(torch.float32)
-    hi = Wp.to(torch.bfloat16)
-    r1 = Wp - hi.float()
-    mid = r1.to(torch.bfloat16)
-    lo = (r1 - mid.float()).to(torch.bfloat16)
-    wsp = torch.stack([t.view(nblk, MAX_K, D) for t in (hi, mid, lo)], dim=1).contiguous()
-    bp = np.zeros(nblk * MAX_K)
-    bp[:K] = b
-    with np.errstate(over="ignore", invalid="ignore"):
-        bh = bp.astype(np.float32)
-        bl = np.where(np.isfinite(bh), bp - bh.astype(np.float64), 0.0).astype(np.float32)
-    return PackedLinear(W, b, wsp.view(torch.int16).numpy(), bh.reshape(nblk, MAX_K), bl.reshape(nblk, MAX_K))
+    terms = split3(pad_rows(torch.from_numpy(W).to(torch.float32), nblk * MAX_K, D))
+    wsp = terms.view(3, nblk, MAX_K, D).transpose(0, 1).contiguous()
+    bp = torch.zeros(nblk * MAX_K, dtype=torch.float64)
+    bp[:K] = torch.from_numpy(b)
+    bh, bl = (t.view(nblk, MAX_K).numpy() for t in hi_lo(bp))
+    return PackedLinear(W, b, wsp.view(torch.int16).numpy(), bh, bl)
 
 
 def model_pack(owner, arrays: tuple, make) -> PackedLinear:

@@ -17,6 +17,7 @@ from dataclasses import dataclass
 import torch
 
 from . import _native as N
+from ._terms import hi_lo, pad_rows, split3
 
 MAX_D = 256      # columns of a row the kernels take
 MAX_H = 128      # hidden units: up to four blocks of 32, one wave each
@@ -102,20 +103,6 @@ class PackedMLP:
     bias: torch.Tensor
 
 
-def _split3(W: torch.Tensor) -> torch.Tensor:
-    hi = W.to(torch.bfloat16)
-    r1 = W - hi.float()
-    mid = r1.to(torch.bfloat16)
-    lo = (r1 - mid.float()).to(torch.bfloat16)
-    return torch.stack([hi, mid, lo])
-
-
-def _hi_lo(b: torch.Tensor):
-    b64 = b.to(torch.float64)
-    hi = b64.float()
-    return hi, (b64 - hi.double()).float()
-
-
 def pack(W1: torch.Tensor, b1: torch.Tensor, W2: torch.Tensor, b2: torch.Tensor, device=None) -> PackedMLP:
     """The device operands of a network (W1 [d, H], b1 [H], W2 [H, K], b2 [K]), built on
     ``device`` (default: where W1 is) with no host sync.  The weights enter at fp32, the biases
@@ -129,22 +116,19 @@ def pack(W1: torch.Tensor, b1: torch.Tensor, W2: torch.Tensor, b2: torch.Tensor,
         raise ValueError(f"MLP kernels take d <= {MAX_D}, H <= {MAX_H}, 2 <= K <= {MAX_K}; got {d}, {H}, {K}")
     dev = torch.device(device) if device is not None else W1.device
     NH, D = -(-H // 32), 32 * (-(-d // 32))
-    W1p = torch.zeros((32 * NH, D), dtype=torch.float32, device=dev)
-    W1p[:H, :d] = W1.to(dev, torch.float32).T
-    W2pad = torch.zeros((32 * NH, 32), dtype=torch.float32, device=dev)
-    W2pad[:H, :K] = W2.to(dev, torch.float32)
+    W1p = pad_rows(W1.to(dev, torch.float32).T, 32 * NH, D)
     idx = k_index().to(dev)
-    t3 = _split3(W2pad).view(3, NH, 32, 32)                        # [t, j, unit, class]
+    t3 = split3(pad_rows(W2.to(dev, torch.float32), 32 * NH, 32)).view(3, NH, 32, 32)   # [t, j, unit, class]
     fwd = t3[:, :, idx, :].permute(1, 2, 0, 3, 5, 4)               # [t, j, s, h, e, c] -> [j, s, t, h, c, e]
     bwd = t3[:, :, :, idx].permute(1, 3, 0, 4, 2, 5)               # [t, j, u, s, h, e] -> [j, s, t, h, u, e]
     W2p = torch.stack([fwd, bwd]).reshape(2, NH, 2, 3, 64, 8).contiguous()
     bias = torch.zeros(64 * NH + 64, dtype=torch.float32, device=dev)
-    b1h, b1l = _hi_lo(b1.to(dev))
-    b2h, b2l = _hi_lo(b2.to(dev))
+    b1h, b1l = hi_lo(b1.to(dev, torch.float64))
+    b2h, b2l = hi_lo(b2.to(dev, torch.float64))
     bias[:H], bias[32 * NH: 32 * NH + H] = b1h, b1l
     bias[64 * NH + K: 64 * NH + 32] = float("-inf")
     bias[64 * NH: 64 * NH + K], bias[64 * NH + 32: 64 * NH + 32 + K] = b2h, b2l
-    return PackedMLP(d, H, K, _split3(W1p).contiguous(), W2p, bias)
+    return PackedMLP(d, H, K, split3(W1p).contiguous(), W2p, bias)
 
 
 def _packed_for(X: torch.Tensor, W1, b1, W2, b2, packed: PackedMLP | None) -> PackedMLP:

@@ -37,6 +37,9 @@ SHAPES = [
     (33, 30, LOSS_SQUARED, True, 7, 0.0, N),
     (40, 3, LOSS_LOGISTIC, True, 0, 0.0, 17),
     (256, 8, LOSS_LOGISTIC, False, 0, 0.0, 100_003),
+    (96, 8, LOSS_LOGISTIC, False, 0, 0.0, 67),        # 3, 5 and 6 column blocks of 32: two full
+    (160, 5, LOSS_SQUARED, True, 0, 0.0, 67),         # tiles and a 3-row tail
+    (192, 30, LOSS_LOGISTIC, True, 8, 0.0, 67),
 ]
 IDS = [f"d{d}-F{F}-{'log' if l == LOSS_LOGISTIC else 'sq'}{'-w' if w else ''}-pad{p}{'-mean2' if m else ''}-n{n}"
        for d, F, l, w, p, m, n in SHAPES]

@@ -176,8 +176,22 @@ def test_gpu_grad_mixed_split_launches_agree(gpu, slice_rows, frac, monkeypatch)
 def test_gpu_softmax_pass_matches_fp64(gpu, d, K, weighted, pad):
     """glm_softmax_kernel (MFMA margins + gradient, split-bf16 W and R) vs the fp64 torch
     pass on the same bf16 rows; padded row strides (vector columns) and ragged tiles."""
+    _softmax_pass_matches_fp64(gpu, 40_003, d, K, weighted, pad)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,d,K,weighted,pad", [
+    (17, 40, 5, True, 0),                # fewer rows than a tile
+    (100_003, 256, 10, False, 0),        # several tiles per wave: prefetch steady state and tail
+    (67, 96, 10, False, 0), (67, 160, 3, True, 0), (67, 192, 32, True, 8)])      # NB = 3, 5, 6
+def test_gpu_softmax_pass_matches_fp64_by_rows(gpu, n, d, K, weighted, pad):
+    """The same check at the row counts of test_softmax_f32.py and on the column-block counts
+    no other case reaches (two full tiles and a 3-row tail)."""
+    _softmax_pass_matches_fp64(gpu, n, d, K, weighted, pad)
+
+
+def _softmax_pass_matches_fp64(gpu, n, d, K, weighted, pad):
     g = torch.Generator().manual_seed(d + K)
-    n = 40_003
     Xf = torch.rand((n, d + pad), generator=g) * 2 - 1
     Xf[:, d:] = 0
     Xb = Xf.to(torch.bfloat16).to(gpu)

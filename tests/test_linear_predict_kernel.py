@@ -42,6 +42,12 @@ CASES = [
     (33, 256, 10, BF16, SCALED),
     (33, 256, 10, F32, SCALED),
     (33, 8, 2, F32, COUNTS),
+    (67, 96, 10, BF16, SCALED),       # 3, 5 and 6 column blocks of 32: two full tiles and a 3-row tail
+    (67, 96, 10, F32, SCALED),
+    (67, 160, 3, BF16, SCALED),
+    (67, 160, 3, F32, SCALED),
+    (67, 192, 32, BF16, SCALED),
+    (67, 192, 32, F32, SCALED),
     (4099, 3, 1, F32, SCALED),
     (4099, 8, 2, BF16, SCALED),
     (4099, 40, 3, BF16, SCALED),

@@ -24,6 +24,9 @@ SHAPES = [
     (33, 32, 32, 7, 0.0, N),           # NH 1 exactly full
     (40, 7, 3, 0, 0.0, 17),            # one partial tile, most slab rows empty
     (256, 32, 10, 0, 0.0, 100_003),    # several tiles per slab row
+    (96, 64, 10, 0, 0.0, 67),          # 3, 5 and 6 column blocks of 32 (as far as the gate takes
+    (160, 32, 5, 0, 0.0, 67),          # them on both row types): two full tiles and a 3-row tail
+    (192, 33, 3, 8, 0.0, 67),
 ]
 IDS = [f"d{d}-H{H}-K{K}-pad{p}{'-mean2' if m else ''}-n{n}" for d, H, K, p, m, n in SHAPES]
 DTYPES = [torch.bfloat16, torch.float32]

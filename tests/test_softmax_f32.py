@@ -41,7 +41,10 @@ SHAPES = [(40_003, 256, 10, False, 0),     # NB = 8
           (40_003, 8, 1, False, 0),        # one chunk; a single class
           (40_003, 33, 32, True, 7),       # NB = 2, only one live column in the second block
           (17, 40, 5, True, 0),            # fewer rows than a tile
-          (100_003, 256, 10, False, 0)]    # several tiles per wave: prefetch steady state and tail
+          (100_003, 256, 10, False, 0),    # several tiles per wave: prefetch steady state and tail
+          (67, 96, 10, False, 0),          # NB = 3, 5 and 6: two full tiles and a 3-row tail
+          (67, 160, 3, True, 0),
+          (67, 192, 32, True, 8)]
 
 
 @pytest.mark.parametrize("d,K", [(256, 10), (20, 3), (100, 32), (8, 5)])
