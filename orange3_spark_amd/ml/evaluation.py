@@ -334,35 +334,48 @@ class ClusteringEvaluator(Evaluator, HasFeaturesCol, HasPredictionCol, HasWeight
         self._set(**self._input_kwargs)
 
     def _evaluate(self, df):
-        from .common import dense_features
+        from ..ops import silhouette as SIL
+        from .common import dense_features, features_column
         g = self.getOrDefault
-        X = dense_features(df, g(self.featuresCol), torch.float64)
-        c = _num(df, g(self.predictionCol)).long().to(X.device)
-        w = _weights(df, self, X.shape[0], X.device)
         comm = df.comm
-        k = int(comm.max_scalar(float(c.max().item()) if c.numel() else 0.0)) + 1
         cosine = g(self.distanceMeasure) == "cosine"
-        if cosine:
-            X = X / X.norm(dim=1, keepdim=True).clamp_min(1e-300)
-        D = X.shape[1]
-        sq = (X * X).sum(1)
-        from ..ops.binsum import bin_sums
-        st = bin_sums(X, c, k, w)          # [sum w x | sum w | sum w ||x||^2] per cluster, no atomics
-        buf = torch.cat([st[:, :D].reshape(-1), st[:, D + 1], st[:, D]])
+        c = _num(df, g(self.predictionCol), None).long()
+        k = int(comm.max_scalar(float(c.max().item()) if c.numel() else 0.0)) + 1
+        # the fused pass (ops/silhouette.py) reads the stored rows; both paths all-reduce the same
+        # two buffers, so ranks may differ in the path they take
+        rows = None
+        if not cosine and SIL.enabled():
+            col = features_column(df, g(self.featuresCol))
+            rows = SIL.column_rows(col, k)
+            if rows is not None and c.numel() and int(c.min()) < 0:
+                rows = None
+        if rows is not None:
+            D = col.size
+            c = c.to(rows.device)
+            w = _weights(df, self, rows.shape[0], rows.device, required=False)
+            Y, N, Psi = SIL.cluster_moments(rows, c, k, w, D)
+            buf = torch.cat([Y.reshape(-1), Psi, N])
+        else:
+            X = dense_features(df, g(self.featuresCol), torch.float64)
+            c = c.to(X.device)
+            w = _weights(df, self, X.shape[0], X.device)
+            if cosine:
+                X = X / X.norm(dim=1, keepdim=True).clamp_min(1e-300)
+            D = X.shape[1]
+            from ..ops.binsum import bin_sums
+            st = bin_sums(X, c, k, w)          # [sum w x | sum w | sum w ||x||^2] per cluster, no atomics
+            buf = torch.cat([st[:, :D].reshape(-1), st[:, D + 1], st[:, D]])
         comm.all_reduce(buf)
         Y, Psi, N = buf[: k * D].reshape(k, D), buf[k * D: k * D + k], buf[k * D + k:]
-        if cosine:
-            dist = 1 - (X @ Y.T) / N.clamp_min(1e-300)[None, :]
+        if rows is not None and int((N > 0).sum()) >= 2:
+            s = SIL.silhouette_rows(rows, D, c, Y, N, Psi).double()
+            t = torch.stack([s.sum(), s.new_tensor(float(s.numel()))] if w is None else [(s * w).sum(), w.sum()])
         else:
-            dist = (sq[:, None] * N[None, :] + Psi[None, :] - 2 * X @ Y.T) / N.clamp_min(1e-300)[None, :]
-        own = dist.gather(1, c[:, None]).squeeze(1)
-        nown = N[c]
-        a = torch.where(nown > 1, own * nown / (nown - 1).clamp_min(1e-300), torch.zeros_like(own))
-        dist.scatter_(1, c[:, None], float("inf"))
-        dist[:, N == 0] = float("inf")
-        b = dist.min(1).values
-        s = torch.where(nown > 1, (b - a) / torch.maximum(a, b).clamp_min(1e-300), torch.zeros_like(a))
-        t = torch.stack([(s * w).sum(), w.sum()])
+            if rows is not None:               # a single non-empty cluster: the formula's own NaN
+                X = rows[:, :D].double()
+                w = torch.ones(X.shape[0], dtype=torch.float64, device=X.device) if w is None else w
+            s = SIL.silhouette_torch(X, c, k, w, Y, N, Psi, cosine=cosine)
+            t = torch.stack([(s * w).sum(), w.sum()])
         comm.all_reduce(t)
         return float(t[0] / t[1])
 

@@ -118,6 +118,8 @@ _SIGS: dict[str, list] = {
     "o3s_gram": [c_vp, c_i32, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp],
     "o3s_gmm_layout": [c_i32, c_i32, C.POINTER(c_i32), C.POINTER(c_i32), C.POINTER(c_i64), C.POINTER(c_i32)],
     "o3s_gmm_estep": [c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp],
+    "o3s_silhouette_layout": [c_i32, c_i32, C.POINTER(c_i32), C.POINTER(c_i32), C.POINTER(c_i64), C.POINTER(c_i32)],
+    "o3s_silhouette": [c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp],
     "o3s_tree_predict_layout": [c_i64, c_i32, c_i32, c_i32, C.POINTER(c_i32), C.POINTER(c_i32)],
     "o3s_tree_predict": [c_vp, c_i32, c_i64, c_i64, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_i32,
                          c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp],
@@ -208,7 +210,7 @@ def host():
 
 PRELOAD_TAGS = ("glm_grad", "glm_mixed", "glm_stats", "glm_softmax", "trees", "kmeans", "als", "als_dense",
                 "als_exact", "assemble", "binsum", "eval", "sampling", "sparse", "text", "probe", "gram", "gmm",
-                "tree_predict", "linear_predict", "fm", "mlp")
+                "tree_predict", "linear_predict", "fm", "mlp", "silhouette")
 
 
 def preload(tags=PRELOAD_TAGS) -> dict:
