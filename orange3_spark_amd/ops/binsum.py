@@ -8,6 +8,8 @@ bin is outside [0, nbins) are ignored.  Host tensors use index_add_.
 """
 from __future__ import annotations
 
+import math
+
 import torch
 
 from . import _native as N
@@ -15,8 +17,13 @@ from . import _native as N
 _DT = {torch.float32: 0, torch.bfloat16: 1, torch.float64: 2}
 
 
+def _rows2d(X: torch.Tensor) -> torch.Tensor:
+    """[n, D] view of the rows (an explicit D: reshape(n, -1) is ambiguous for n = 0)."""
+    return X if X.dim() == 2 else X.reshape(X.shape[0], math.prod(X.shape[1:]))
+
+
 def bin_sums_torch(X: torch.Tensor, bins: torch.Tensor, nbins: int, w: torch.Tensor | None = None) -> torch.Tensor:
-    X2 = X.reshape(X.shape[0], -1).to(torch.float64)
+    X2 = _rows2d(X).to(torch.float64)
     b = bins.to(X2.device).long()
     ok = (b >= 0) & (b < nbins)
     b, X2 = b[ok], X2[ok]
@@ -29,14 +36,14 @@ def bin_sums_torch(X: torch.Tensor, bins: torch.Tensor, nbins: int, w: torch.Ten
 
 
 def kernel_ok(X: torch.Tensor) -> bool:
-    X2 = X if X.dim() == 2 else X.reshape(X.shape[0], -1)
+    X2 = _rows2d(X)
     return X.is_cuda and X.dtype in _DT and X2.stride(-1) == 1 and 1 <= X2.shape[1] <= 256
 
 
 def bin_sums(X: torch.Tensor, bins: torch.Tensor, nbins: int, w: torch.Tensor | None = None) -> torch.Tensor:
     if not kernel_ok(X) or nbins < 1:
         return bin_sums_torch(X, bins, nbins, w)
-    X2 = X if X.dim() == 2 else X.reshape(X.shape[0], -1)
+    X2 = _rows2d(X)
     n, D = X2.shape
     dev = X.device
     b64 = bins.to(dev, torch.int64).contiguous()

@@ -78,9 +78,10 @@ __global__ __launch_bounds__(kEvalThreads) void confusion_kernel(
   __syncthreads();
   const int64_t stride = (int64_t)gridDim.x * kEvalThreads;
   for (int64_t i = (int64_t)blockIdx.x * kEvalThreads + threadIdx.x; i < n; i += stride) {
-    int a = (int)ld_num(y, ydt, i), b = (int)ld_num(p, pdt, i);
-    a = min(max(a, 0), k - 1);
-    b = min(max(b, 0), k - 1);
+    // clamped in floating point, then converted (an out-of-range double -> int is undefined)
+    const double top = (double)(k - 1);
+    const int a = (int)fmin(fmax(ld_num(y, ydt, i), 0.0), top);
+    const int b = (int)fmin(fmax(ld_num(p, pdt, i), 0.0), top);
     const double ww = w ? ld_num(w, wdt, i) : 1.0;
     atomicAdd(&cm[a * k + b], ww);
   }
@@ -96,8 +97,9 @@ __global__ __launch_bounds__(kEvalThreads) void score_hist_kernel(
     const double sc = ld_num(s, sdt, i * pstride);
     const double yy = ld_num(y, ydt, i);
     const double ww = w ? ld_num(w, wdt, i) : 1.0;
-    int b = (int)((sc - lo) * scale);
-    b = min(max(b, 0), bins - 1);
+    // clamp in floating point, then convert: an out-of-range double -> int is undefined
+    // (fmax / fmin drop a NaN operand, so a NaN score counts in bin 0; unspecified)
+    const int b = (int)fmin(fmax((sc - lo) * scale, 0.0), (double)(bins - 1));
     // class 0 = positive (label > 0.5), 1 = negative
     atomicAdd(&hist[(yy > 0.5 ? 0 : bins) + b], ww);
   }
@@ -125,7 +127,10 @@ O3S_API int o3s_eval_grid(int64_t n) { return eval_grid(n); }
 
 O3S_API int o3s_regression_stats(const void* y, int ydt, const void* p, int pdt, const void* w, int wdt, int64_t n,
                                  double* slab, double* out, hipStream_t st) {
-  if (n < 0 || !y || !p || !slab || !out) return -1;
+  if (n < 0 || !slab || !out) return -1;
+  if (n == 0)                                  // an empty shard: its columns have no storage (null pointers)
+    return hipMemsetAsync(out, 0, 7 * sizeof(double), st) == hipSuccess ? 0 : -3;
+  if (!y || !p) return -1;
   const int g = eval_grid(n);
   regression_stats_kernel<<<g, kEvalThreads, 0, st>>>(y, ydt, p, pdt, w, wdt, n, slab);
   slab_sum_kernel<<<1, 64, 0, st>>>(slab, g, 7, 8, out);
@@ -135,7 +140,9 @@ O3S_API int o3s_regression_stats(const void* y, int ydt, const void* p, int pdt,
 // slab: >= grid * k * k doubles; out: k * k doubles.  k <= 64.
 O3S_API int o3s_confusion(const void* y, int ydt, const void* p, int pdt, const void* w, int wdt, int64_t n, int k,
                           double* slab, double* out, hipStream_t st) {
-  if (n < 0 || k < 1 || k > 64 || !y || !p || !slab || !out) return -1;
+  if (n < 0 || k < 1 || k > 64 || !slab || !out) return -1;
+  if (n == 0) return hipMemsetAsync(out, 0, (size_t)k * k * sizeof(double), st) == hipSuccess ? 0 : -3;
+  if (!y || !p) return -1;
   const int g = eval_grid(n);
   confusion_kernel<<<g, kEvalThreads, (size_t)k * k * sizeof(double), st>>>(y, ydt, p, pdt, w, wdt, n, k, slab);
   const int kk = k * k;
@@ -146,7 +153,9 @@ O3S_API int o3s_confusion(const void* y, int ydt, const void* p, int pdt, const 
 // hist: 2 * bins doubles, zeroed by the caller (positives first, then negatives).
 O3S_API int o3s_score_hist(const void* s, int sdt, int64_t pstride, const void* y, int ydt, const void* w, int wdt,
                            int64_t n, double lo, double span, int bins, double* hist, hipStream_t st) {
-  if (n < 0 || bins < 1 || !s || !y || !hist || !(span > 0)) return -1;
+  if (n < 0 || bins < 1 || !hist || !(span > 0)) return -1;
+  if (n == 0) return 0;                        // nothing to count: hist stays as the caller zeroed it
+  if (!s || !y) return -1;
   const double scale = (double)(bins - 1) / span;
   score_hist_kernel<<<eval_grid(n), kEvalThreads, 0, st>>>(s, sdt, pstride, y, ydt, w, wdt, n, lo, scale, bins, hist);
   return (int)hipGetLastError();

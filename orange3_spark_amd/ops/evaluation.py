@@ -49,8 +49,10 @@ def regression_stats(y, p, w=None):
 
 
 def confusion_torch(y, p, k, w=None):
-    yl = y.to(torch.float64).long().clamp(0, k - 1)
-    pl = p.to(torch.float64).long().clamp(0, k - 1)
+    """Labels / predictions outside [0, k) count in the first / last class: clamped in
+    floating point, then truncated, as in the kernel (NaN: class 0, unspecified)."""
+    yl = y.to(torch.float64).clamp(0, k - 1).nan_to_num(nan=0.0).long()
+    pl = p.to(torch.float64).clamp(0, k - 1).nan_to_num(nan=0.0).long()
     w64 = torch.ones(y.shape[0], dtype=torch.float64, device=y.device) if w is None else w.to(torch.float64)
     return torch.zeros(k * k, dtype=torch.float64, device=y.device).index_add_(0, yl * k + pl, w64).reshape(k, k)
 
@@ -69,8 +71,11 @@ def confusion(y, p, k, w=None):
 
 
 def score_hist_torch(score, y, lo, span, bins, w=None):
+    """Scores outside [lo, lo + span] (+-inf included) count in the first / last bin: the
+    bin position is clamped in floating point, then converted, as in the kernel.  The bin
+    of a NaN score is unspecified (today: bin 0 on both paths)."""
     s = score.to(torch.float64)
-    b = ((s - lo) * ((bins - 1) / span)).to(torch.int64).clamp(0, bins - 1)
+    b = ((s - lo) * ((bins - 1) / span)).clamp(0, bins - 1).nan_to_num(nan=0.0).to(torch.int64)
     neg = (y.to(torch.float64) <= 0.5).to(torch.int64)
     w64 = torch.ones_like(s) if w is None else w.to(torch.float64)
     return torch.zeros(2 * bins, dtype=torch.float64, device=s.device).index_add_(0, neg * bins + b, w64).reshape(2, bins)

@@ -23,7 +23,8 @@ class SparseRows:
         self._csc = False
         if self.kernel:
             self.grid = max(1, min(N.num_cus(dev) * 8, (self.n + 31) // 32))
-            self.slab = torch.empty(self.grid * 3, dtype=torch.float32, device=dev)
+            # zeroed: with no rows nothing is launched, and loss_grad still sums the slab
+            self.slab = torch.zeros(self.grid * 3, dtype=torch.float32, device=dev)
 
     def _build_csc(self):
         """CSC copy + gradient piece plan, built on first use (a transform needs neither)."""

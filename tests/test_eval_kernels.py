@@ -124,3 +124,258 @@ def test_gpu_exact_curve_matches_host(gpu):
     for a, b in zip(host[:3], dev[:3]):
         assert a.shape == b.shape and np.allclose(a, b, rtol=1e-10)
     assert abs(host[3] - dev[3]) < 1e-6 and abs(host[4] - dev[4]) < 1e-6
+
+
+# ------------------------------------------------------------------------------------------
+# Exact-arithmetic edge tests.  Labels / predictions are integers in [-100, 100] and weights
+# are k/8, so every term and every partial sum of the fp64 accumulators is an exact multiple
+# of 1/8 far below 2^53: the kernels must equal the torch references bitwise, whatever the
+# reduction order.  The condition is asserted on the inputs by an unmarked test.
+
+F64_EXACT = 1 << 53
+EVAL_DTYPES = [torch.float32, torch.float64, torch.int64, torch.int32]
+W_DTYPES = [None, torch.float32, torch.float64]
+EVAL_NS = [0, 1, 255, 256, 257, 2048, 2049]          # o3s_eval_grid = ceil(n / 2048): 2049 = two blocks
+CONF_KS = [1, 2, 16, 17, 64]
+HIST_BINS = [1, 2, 1 << 16]
+HIST_LO, HIST_SPAN = -4.0, 8.0
+_ID = lambda d: "none" if d is None else str(d).replace("torch.", "")
+
+
+def _eval_case(n, seed=0):
+    """(y, p, w) as int64 / int64 / float64 masters: integers in [-100, 100], weights k/8."""
+    g = torch.Generator().manual_seed(100 + n + seed)
+    y = torch.randint(-100, 101, (n,), generator=g)
+    p = torch.randint(-100, 101, (n,), generator=g)
+    w = torch.randint(0, 17, (n,), generator=g).double() / 8
+    return y, p, w
+
+
+def _label_case(n, k, seed=0):
+    """Class labels / predictions in [-3, k + 2]: outside [0, k) on both sides."""
+    g = torch.Generator().manual_seed(200 + n + k + seed)
+    return (torch.randint(-3, k + 3, (n,), generator=g), torch.randint(-3, k + 3, (n,), generator=g),
+            torch.randint(0, 17, (n,), generator=g).double() / 8)
+
+
+def _hist_case(n, int_scores=False, seed=0):
+    """(raw [n, 2], label, w): column 1 holds the score -- multiples of 1/16 in [-6, 6]
+    (below lo = -4 and above lo + span = 4 included) and the out-of-range specials first."""
+    g = torch.Generator().manual_seed(300 + n + seed)
+    if int_scores:
+        raw = torch.randint(-6, 7, (n, 2), generator=g)
+        special = torch.tensor([1 << 62, -(1 << 62), 10 ** 18, -(10 ** 18)])
+    else:
+        raw = torch.randint(-96, 97, (n, 2), generator=g).double() / 16
+        special = torch.tensor([float("inf"), float("-inf"), 1e30, -1e30], dtype=torch.float64)
+    m = min(n, special.numel())
+    raw[:m, 1] = special[:m]
+    lab = torch.randint(0, 2, (n,), generator=g).double()
+    lab[:m] = torch.tensor([1.0, 0.0, 0.0, 1.0])[:m]
+    w = torch.randint(0, 17, (n,), generator=g).double() / 8
+    return raw, lab, w
+
+
+def eval_abs_bound(y, p, w):
+    """Largest regression_stats sum with every term replaced by its absolute value, in
+    units of 1/8 (the weight spacing)."""
+    y, p = y.double().abs(), p.double().abs()
+    w = torch.ones_like(y) if w is None else w.double().abs()
+    e = y + p
+    return 8.0 * float(max([t.sum() for t in (w, w * e * e, w * e, w * y, w * y * y, w * p, w * p * p)],
+                           default=torch.zeros(())))
+
+
+@pytest.mark.parametrize("n", EVAL_NS)
+def test_eval_inputs_are_exact_in_fp64(n):
+    y, p, w = _eval_case(n)
+    assert torch.equal(w * 8, (w * 8).round())
+    assert eval_abs_bound(y, p, w) < F64_EXACT and eval_abs_bound(y, p, None) < F64_EXACT
+    for k in CONF_KS + [65]:
+        yc, pc, wc = _label_case(n, k)
+        assert 8.0 * float(wc.sum()) < F64_EXACT and n < F64_EXACT
+        if n >= 255:
+            assert int(yc.min()) < 0 and int(yc.max()) >= k and int(pc.min()) < 0 and int(pc.max()) >= k
+    for ints in (False, True):
+        raw, lab, wh = _hist_case(n, ints)
+        assert 8.0 * float(wh.sum()) < F64_EXACT
+        if n >= 255:
+            s = raw[:, 1].double()
+            assert bool((s < HIST_LO).any()) and bool((s > HIST_LO + HIST_SPAN).any())
+
+
+def test_score_hist_torch_clamps_before_converting():
+    """+inf and 1e30 count in the last bin, -inf and -1e30 in the first (the reference used
+    to convert to int64 first, which sent all four to bin 0)."""
+    s = torch.tensor([float("inf"), float("-inf"), 0.5, 1e30, -1e30], dtype=torch.float64)
+    y = torch.ones(5)
+    assert EV.score_hist_torch(s, y, 0.0, 1.0, 8)[0].tolist() == [2.0, 0, 0, 1.0, 0, 0, 0, 2.0]
+    assert EV.score_hist_torch(s.float(), y, 0.0, 1.0, 8)[0].tolist() == [2.0, 0, 0, 1.0, 0, 0, 0, 2.0]
+    assert EV.score_hist_torch(s, 1 - y, 0.0, 1.0, 1).tolist() == [[0.0], [5.0]]
+    big = torch.tensor([1 << 62, -(1 << 62), 0])
+    assert EV.score_hist_torch(big, y[:3], -4.0, 8.0, 2)[0].tolist() == [2.0, 1.0]
+    for bins in HIST_BINS:
+        raw, lab, w = _hist_case(2049)
+        h = EV.score_hist_torch(raw[:4, 1], lab[:4], HIST_LO, HIST_SPAN, bins)
+        assert h[0, bins - 1] >= 1 and h[1, 0] >= 1 and float(h.sum()) == 4.0   # +inf (positive), -inf (negative)
+
+
+def _far_labels(dt):
+    """(labels, predictions) far outside the int range, and in-range neighbours."""
+    if dt == torch.int64:
+        return torch.tensor([1 << 62, -(1 << 62), 2, 10 ** 18]), torch.tensor([-(10 ** 18), 1 << 62, 2, 0])
+    return (torch.tensor([float("inf"), float("-inf"), 2.0, 1e30], dtype=dt),
+            torch.tensor([-1e30, float("inf"), 2.0, 0.0], dtype=dt))
+
+
+FAR_WANT = [(4, 0), (0, 4), (2, 2), (4, 0)]          # (label, prediction) cells for k = 5
+
+
+@pytest.mark.parametrize("dt", [torch.float32, torch.float64, torch.int64], ids=_ID)
+def test_confusion_torch_clamps_before_converting(dt):
+    y, p = _far_labels(dt)
+    want = torch.zeros((5, 5), dtype=torch.float64)
+    for a, b in FAR_WANT:
+        want[a, b] += 1
+    assert torch.equal(EV.confusion_torch(y, p, 5), want)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dt", [torch.float32, torch.float64, torch.int64], ids=_ID)
+def test_gpu_confusion_far_out_of_range_labels(gpu, dt):
+    """+-inf, +-1e30 and +-2^62 count in the first / last class on the kernel as well."""
+    y, p = _far_labels(dt)
+    assert torch.equal(EV.confusion(y.to(gpu), p.to(gpu), 5).cpu(), EV.confusion_torch(y, p, 5))
+
+
+def test_eval_torch_references_on_empty_input():
+    e = torch.zeros(0)
+    assert torch.equal(EV.regression_stats(e, e), torch.zeros(7, dtype=torch.float64))
+    assert torch.equal(EV.confusion(e, e, 3), torch.zeros((3, 3), dtype=torch.float64))
+    assert torch.equal(EV.score_hist(e, e, 0.0, 1.0, 4), torch.zeros((2, 4), dtype=torch.float64))
+
+
+def _cast(t, dt, dev):
+    return None if dt is None else t.to(dt).to(dev)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("wdt", W_DTYPES, ids=_ID)
+@pytest.mark.parametrize("pdt", EVAL_DTYPES, ids=_ID)
+@pytest.mark.parametrize("ydt", EVAL_DTYPES, ids=_ID)
+def test_gpu_regression_and_confusion_dtype_pairs_bitwise(gpu, ydt, pdt, wdt):
+    """Every (label, prediction) dtype code pair with unit, fp32 and fp64 weights."""
+    n, k = 2049, 17
+    y, p, w = _eval_case(n)
+    got = EV.regression_stats(_cast(y, ydt, gpu), _cast(p, pdt, gpu), _cast(w, wdt, gpu))
+    assert got.is_cuda and got.dtype == torch.float64
+    assert torch.equal(got.cpu(), EV.regression_stats_torch(y, p, None if wdt is None else w))
+    yc, pc, wc = _label_case(n, k)
+    got = EV.confusion(_cast(yc, ydt, gpu), _cast(pc, pdt, gpu), k, _cast(wc, wdt, gpu))
+    ref = EV.confusion_torch(yc, pc, k, None if wdt is None else wc)
+    assert got.is_cuda and torch.equal(got.cpu(), ref)
+    assert float(ref.sum()) == float(n if wdt is None else wc.sum())
+
+
+@pytest.mark.gpu
+def test_gpu_eval_other_dtypes_are_converted(gpu):
+    """int16 / float16 columns are not kernel dtypes: _operand converts them."""
+    n = 2049
+    y, p, w = _eval_case(n)
+    ref = EV.regression_stats_torch(y, p, w)
+    for a, b in ((torch.int16, torch.float16), (torch.float16, torch.int16)):
+        got = EV.regression_stats(y.to(a).to(gpu), p.to(b).to(gpu), w.to(torch.float16).to(gpu))
+        assert torch.equal(got.cpu(), ref)
+        yc, pc, wc = _label_case(n, 16)
+        got = EV.confusion(yc.to(a).to(gpu), pc.to(b).to(gpu), 16, wc.to(torch.float16).to(gpu))
+        assert torch.equal(got.cpu(), EV.confusion_torch(yc, pc, 16, wc))
+    raw, lab, wh = _hist_case(n)
+    got = EV.score_hist(raw[:, 1].to(torch.float16).to(gpu), lab.to(torch.int16).to(gpu), HIST_LO, HIST_SPAN, 64,
+                        wh.to(torch.float16).to(gpu))
+    assert torch.equal(got.cpu(), EV.score_hist_torch(raw[:, 1].to(torch.float16), lab, HIST_LO, HIST_SPAN, 64, wh))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", EVAL_NS)
+def test_gpu_regression_stats_row_counts_bitwise(gpu, n):
+    y, p, w = _eval_case(n)
+    for ww in (None, w):
+        got = EV.regression_stats(y.float().to(gpu), p.double().to(gpu), _cast(w, None if ww is None else torch.float32, gpu))
+        assert got.is_cuda and got.shape == (7,)
+        assert torch.equal(got.cpu(), EV.regression_stats_torch(y, p, ww))
+    if n == 0:
+        assert not got.any()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k", CONF_KS + [65])
+@pytest.mark.parametrize("n", EVAL_NS)
+def test_gpu_confusion_classes_and_row_counts_bitwise(gpu, n, k):
+    """k = 1 .. 64 on the LDS-privatised kernel, k = 65 on torch; labels and predictions
+    outside [0, k) are clamped into the first / last class by both."""
+    yc, pc, wc = _label_case(n, k)
+    for ww in (None, wc):
+        got = EV.confusion(yc.to(gpu), pc.to(torch.int32).to(gpu), k, None if ww is None else ww.to(gpu))
+        assert got.is_cuda and got.shape == (k, k)
+        assert torch.equal(got.cpu(), EV.confusion_torch(yc, pc, k, ww))
+    if n == 0:
+        assert not got.any()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("bins", HIST_BINS)
+@pytest.mark.parametrize("layout", ["column-float32", "column-float64", "contiguous-float32", "contiguous-int64"])
+def test_gpu_score_hist_layouts_and_out_of_range_bitwise(gpu, layout, bins):
+    """The score read in place from column 1 of an [n, 2] matrix (pstride = 2) or from a
+    contiguous column; scores below lo and above lo + span, +-1e30 and +-inf (+-2^62 for
+    int64) land in bin 0 and bin bins - 1 on the kernel as on the reference."""
+    n = 2049
+    kind, dt = layout.split("-")
+    dt = getattr(torch, dt)
+    raw, lab, w = _hist_case(n, int_scores=dt == torch.int64)
+    raw = raw.to(dt)
+    dev_raw = raw.to(gpu)
+    score = dev_raw[:, 1] if kind == "column" else dev_raw[:, 1].contiguous()
+    assert score.stride(0) == (2 if kind == "column" else 1)
+    for ww in (None, w):
+        got = EV.score_hist(score, lab.float().to(gpu), HIST_LO, HIST_SPAN, bins, None if ww is None else ww.to(gpu))
+        ref = EV.score_hist_torch(raw[:, 1], lab, HIST_LO, HIST_SPAN, bins, ww)
+        assert got.is_cuda and got.shape == (2, bins)
+        assert torch.equal(got.cpu(), ref)
+    # the four specials alone: {+big: positive, -big: negative, +big: negative, -big: positive}
+    got = EV.score_hist(score[:4], lab[:4].to(gpu), HIST_LO, HIST_SPAN, bins).cpu()
+    want = torch.zeros((2, bins), dtype=torch.float64)
+    want[0, bins - 1] += 1
+    want[1, 0] += 1
+    want[1, bins - 1] += 1
+    want[0, 0] += 1
+    assert torch.equal(got, want)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", EVAL_NS)
+def test_gpu_score_hist_row_counts_bitwise(gpu, n):
+    raw, lab, w = _hist_case(n)
+    got = EV.score_hist(raw.float().to(gpu)[:, 1], lab.to(gpu), HIST_LO, HIST_SPAN, 256, w.float().to(gpu))
+    assert got.is_cuda and got.shape == (2, 256)
+    assert torch.equal(got.cpu(), EV.score_hist_torch(raw.float()[:, 1], lab, HIST_LO, HIST_SPAN, 256, w))
+    if n == 0:
+        assert not got.any()
+
+
+@pytest.mark.gpu
+def test_gpu_evaluators_on_an_empty_shard(gpu):
+    """An empty device column has no storage (data_ptr() == 0): zeros of the right shape on
+    the device, no error, for every dtype code and with weights."""
+    for dt in EVAL_DTYPES:
+        e = torch.zeros(0, dtype=dt, device=gpu)
+        for w in (None, torch.zeros(0, device=gpu)):
+            assert e.data_ptr() == 0
+            r = EV.regression_stats(e, e, w)
+            assert r.is_cuda and torch.equal(r.cpu(), torch.zeros(7, dtype=torch.float64))
+            c = EV.confusion(e, e, 5, w)
+            assert c.is_cuda and torch.equal(c.cpu(), torch.zeros((5, 5), dtype=torch.float64))
+            h = EV.score_hist(e, e, 0.0, 1.0, 9, w)
+            assert h.is_cuda and torch.equal(h.cpu(), torch.zeros((2, 9), dtype=torch.float64))
+    h = EV.score_hist(torch.zeros((0, 2), device=gpu)[:, 1], torch.zeros(0, device=gpu), 0.0, 1.0, 9)
+    assert h.is_cuda and h.shape == (2, 9) and not h.any()
