@@ -208,9 +208,9 @@ def host():
     return _HOST
 
 
-PRELOAD_TAGS = ("glm_grad", "glm_mixed", "glm_stats", "glm_softmax", "trees", "kmeans", "als", "als_dense",
-                "als_exact", "assemble", "binsum", "eval", "sampling", "sparse", "text", "probe", "gram", "gmm",
-                "tree_predict", "linear_predict", "fm", "mlp", "silhouette")
+PRELOAD_TAGS = ("glm_grad", "glm_mixed", "glm_stats", "glm_softmax", "trees", "kmeans_assign", "kmeans_update",
+                "kmeans_init", "als", "als_dense", "als_exact", "assemble", "binsum", "eval", "sampling", "sparse",
+                "text", "probe", "gram", "gmm", "tree_predict", "linear_predict", "fm", "mlp", "silhouette")
 
 
 def preload(tags=PRELOAD_TAGS) -> dict:

@@ -13,6 +13,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #define O3S_API extern "C" __attribute__((visibility("default")))
 
 namespace o3s {
@@ -119,6 +121,13 @@ __device__ __forceinline__ float sigmoidf(float x) {
 __device__ __forceinline__ int xcd_remap(int orig, int nwg) {
   const int q = nwg / 8, r = nwg % 8, xcd = orig % 8;
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + orig / 8;
+}
+
+// Host dispatch of a run-time flag to a template argument: f gets the flag as
+// std::true_type / std::false_type and returns the entry point's return code.
+template <class F>
+int with_bool(bool flag, F&& f) {
+  return flag ? f(std::true_type{}) : f(std::false_type{});
 }
 
 }  // namespace o3s

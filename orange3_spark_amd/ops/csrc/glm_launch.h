@@ -115,11 +115,6 @@ int with_loss(int loss, F&& f) {
   if (loss == LOSS_HINGE) return f(IC<LOSS_HINGE>{});
   return f(IC<LOSS_SQUARED>{});
 }
-// f gets the flag as std::true_type / std::false_type.
-template <class F>
-int with_bool(bool flag, F&& f) {
-  return flag ? f(std::true_type{}) : f(std::false_type{});
-}
 template <class F>
 int with_remapped_layout_and_loss(const Layout& l, int loss, F&& f) {
   return with_remapped_layout(l, [&](auto L, auto C) {

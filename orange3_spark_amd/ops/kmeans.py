@@ -1,4 +1,5 @@
-"""KMeans assign/update ops: gfx950 kernels (csrc/kmeans.hip) with PyTorch references.
+"""KMeans assign/update ops: gfx950 kernels (csrc/kmeans_assign.hip, csrc/kmeans_update.hip)
+with PyTorch references.
 
 ``assign`` returns (cluster index int32 [n], squared distance f32 [n]); ``update`` returns
 fp64 per-cluster (sums [K, D], counts [K]) of this rank's rows (caller all-reduces).
@@ -32,9 +33,6 @@ class Prepared:
         # without the measured errors: the worst case of fp16 rounding (2^-11 per element)
         self.dm = 2.0 ** -10 * cmax if dm is None else dm
         self.mmax = 2.0 * cmax * (1 + 2.0 ** -10) if mmax is None else mmax
-
-    def __iter__(self):                         # legacy (hi, lo, cn) unpacking
-        return iter((self.hi, self.lo, self.cn))
 
 
 def prepare_centers(C: torch.Tensor) -> Prepared:
@@ -260,6 +258,26 @@ def screen_ok(X: torch.Tensor, Kp: int | None = None) -> bool:
     return kernel_ok(X) and X.shape[0] < 2 ** 31 and (Kp is None or screen_fits(X.shape[1], Kp))
 
 
+def _screen(X, P: "Prepared", n: int, a, d, pair: bool, rows, bnd, tag: str):
+    """One launch of the screen kernel over n rows of X (``rows``: their int32 indices; None:
+    the first n), writing ``a[row]``, the squared distance ``d[row]`` and the Hamerly bounds
+    ``bnd[row]`` (d, bnd: None = not wanted).  ``pair``: the top-3 build, which reads the fp32
+    rows; the plain screen takes the pre-split rows when there are any.  Returns the near-tie
+    buffers (counter, row list) of ``_SWS``."""
+    cnt, flag = _SWS.get(n, X.device)
+    cnt.zero_()
+    xs = x_scale(X)
+    eps_x, eps0, eps_e = screen_bound(P, xs, X.shape[1])
+    xp, xn = (None if pair else presplit(X, xs)) or (None, None)
+    tt = SCREEN_TT or (2 if X.shape[1] <= 128 else 1)
+    N.check(N.kernels().o3s_kmeans_screen2(
+        X.data_ptr(), n, X.stride(0), X.shape[1], P.h16.data_ptr(), P.cn.data_ptr(), P.c32.data_ptr(),
+        P.c32.stride(0), P.hi.shape[0], Ct.c_float(eps_x), Ct.c_float(eps0), Ct.c_float(eps_e * P.ms), Ct.c_float(xs),
+        Ct.c_float(xs * P.ms), a.data_ptr(), N.ptr(d), cnt.data_ptr(), flag.data_ptr(), tt, int(pair), N.ptr(xp),
+        N.ptr(xn), N.ptr(rows), N.ptr(bnd), N.stream_of(X)), tag)
+    return cnt, flag
+
+
 def assign(X: torch.Tensor, C: torch.Tensor, prepared=None, mode: str = "auto", stats: dict | None = None,
            need_dist: bool = True):
     """(cluster int32 [n], squared distance f32 [n]) of every row of X.  ``need_dist=False``
@@ -309,34 +327,10 @@ def assign(X: torch.Tensor, C: torch.Tensor, prepared=None, mode: str = "auto", 
     if stats is not None:
         stats["mode"] = mode
     if approx and mode == "screen":
-        cnt, rows = _SWS.get(n, X.device)
-        cnt.zero_()                              # the kernel still lists its near ties (< n rows)
-        xs = x_scale(X)
-        eps_x, eps0, eps_e = screen_bound(P, xs, X.shape[1])
-        ps = presplit(X, xs)
-        tt = SCREEN_TT or (2 if X.shape[1] <= 128 else 1)
-        N.check(lib.o3s_kmeans_screen2(X.data_ptr(), n, X.stride(0), X.shape[1], P.h16.data_ptr(), P.cn.data_ptr(),
-                                       P.c32.data_ptr(), P.c32.stride(0), P.hi.shape[0], Ct.c_float(eps_x),
-                                       Ct.c_float(eps0), Ct.c_float(eps_e * P.ms), Ct.c_float(xs),
-                                       Ct.c_float(xs * P.ms), a.data_ptr(), N.ptr(d), cnt.data_ptr(), rows.data_ptr(),
-                                       tt, 0, N.ptr(ps[0]) if ps else None, N.ptr(ps[1]) if ps else None, None, None,
-                                       st),
-                "kmeans_screen")
+        _screen(X, P, n, a, d, False, None, None, "kmeans_screen")   # its near-tie list is not read
         return a, d
     if mode in ("screen", "pair") and fits:
-        cnt, rows = _SWS.get(n, X.device)
-        cnt.zero_()
-        tt = SCREEN_TT or (2 if X.shape[1] <= 128 else 1)
-        xs = x_scale(X)
-        eps_x, eps0, eps_e = screen_bound(P, xs, X.shape[1])
-        ps = presplit(X, xs) if mode == "screen" else None
-        N.check(lib.o3s_kmeans_screen2(X.data_ptr(), n, X.stride(0), X.shape[1], P.h16.data_ptr(), P.cn.data_ptr(),
-                                       P.c32.data_ptr(), P.c32.stride(0), P.hi.shape[0], Ct.c_float(eps_x),
-                                       Ct.c_float(eps0), Ct.c_float(eps_e * P.ms), Ct.c_float(xs),
-                                       Ct.c_float(xs * P.ms), a.data_ptr(), N.ptr(d), cnt.data_ptr(), rows.data_ptr(),
-                                       tt, int(mode == "pair"), N.ptr(ps[0]) if ps else None,
-                                       N.ptr(ps[1]) if ps else None, None, None, st),
-                "kmeans_screen")
+        cnt, rows = _screen(X, P, n, a, d, mode == "pair", None, None, "kmeans_screen")
         m = int(cnt.item())                      # the near-tie count sizes the re-solve grid
         frac = m / max(n, 1)
         if mode == "screen" and PAIR_FROM is not None and frac > PAIR_FROM:
@@ -390,19 +384,7 @@ def assign_bounded(X: torch.Tensor, P: Prepared, a: torch.Tensor, bnd: torch.Ten
         if stats is not None:
             stats["screened"] = stats["flagged"] = n
         return
-    cnt, flag = _SWS.get(n, X.device)
-    cnt.zero_()
-    xs = x_scale(X)
-    eps_x, eps0, eps_e = screen_bound(P, xs, X.shape[1])
-    ps = presplit(X, xs)
-    tt = SCREEN_TT or (2 if X.shape[1] <= 128 else 1)
-    N.check(lib.o3s_kmeans_screen2(X.data_ptr(), n, X.stride(0), X.shape[1], P.h16.data_ptr(), P.cn.data_ptr(),
-                                   P.c32.data_ptr(), P.c32.stride(0), P.hi.shape[0], Ct.c_float(eps_x),
-                                   Ct.c_float(eps0), Ct.c_float(eps_e * P.ms), Ct.c_float(xs), Ct.c_float(xs * P.ms),
-                                   a.data_ptr(), None,
-                                   cnt.data_ptr(), flag.data_ptr(), tt, 0, N.ptr(ps[0]) if ps else None,
-                                   N.ptr(ps[1]) if ps else None, N.ptr(rows), bnd.data_ptr(), st),
-            "kmeans_screen(bounds)")
+    cnt, flag = _screen(X, P, n, a, None, False, rows, bnd, "kmeans_screen(bounds)")
     m = int(cnt.item())
     if stats is not None:
         stats["screened"] = n

@@ -1,4 +1,4 @@
-"""K-means kernels (ops/csrc/kmeans.hip) at every shape their host entry points dispatch on,
+"""K-means kernels (ops/csrc/kmeans_assign.hip, kmeans_update.hip) at every shape their host entry points dispatch on,
 each against an fp64 torch reference.  The test that owns each variant:
 
   kmeans_assign_kernel<KS,1,true>   KS 2..10       test_gpu_split_assign_every_width
